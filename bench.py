@@ -7,7 +7,13 @@ already resident in HBM.  Weights are the committed H36M fixture state dict
 (tests/golden/model_h36m.npz: random init, dynamic terms randomised, BN
 calibrated), so activations stay finite; values do not change the work.
 
-  python bench.py [--gpus N --steps K --warmup W] [--global-batch G]
+  python bench.py [--gpus N --steps K --warmup W] [--global-batch G] [--full] [--dump-outputs DIR]
+  plain: set-up, W warm-up steps, the settle period, the K timed steps, the line.
+  --dump-outputs DIR: what model(x) returned in the last timed step, as
+         DIR/y.npy (float32 [B][T][V][3]); weights and the seeded input are the
+         same from run to run, so two builds compare output for output.
+  --full: also the untimed profiled pass and the event probes behind
+         `roofline`, the side legs and the CPU baselines (below).
   N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
          weak scaling (default): every rank runs its own B=256 shard;
          --global-batch G: strong scaling, G sequences split over the ranks
@@ -17,7 +23,7 @@ calibrated), so activations stay finite; values do not change the work.
 Timing: barrier + synchronize, t0, exactly K steps, synchronize, t1, barrier
 (the barriers bracket the region but are not inside it).
 
-One JSON line on rank 0.  Besides the driver's fields it carries
+One JSON line on rank 0.  With --full, besides the driver's fields it carries
   roofline     : the dominant kernel family (largest summed time per step in
                  an untimed profiled pass; at B >= the CU count the block
                  kernel, one launch per DSTDGCB) and its launch in DSTDGCB 1
@@ -487,6 +493,13 @@ def main():
     ap.add_argument("--probe-every", type=int, default=5,
                     help="bracket the dominant launch with HIP events in one of every P timed steps "
                          "(an event pair costs ~5%% of a step)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the untimed profiled pass and the event probes "
+                         "behind `roofline`, the side legs (other configs, exact fp32, B=32 eval, training step) "
+                         "and the CPU baselines; without it the run warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step's model(x) returned as "
+                         "DIR/y.npy (float32; DIR/y_rank<r>.npy per rank at N > 1)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -528,8 +541,7 @@ def main():
     B = x_cpu.shape[0]
     x = x_cpu.to(device)
     y = torch.empty_like(x)
-    L = native.lib()
-    fl = model_block_flops(opts, model.gc_arithmetic == "split")
+    split_on = model.gc_arithmetic == "split"
 
     def barrier():
         if dist is not None:
@@ -547,30 +559,35 @@ def main():
             torch.cuda.synchronize()
             settle_steps += 10
 
-        # untimed pass: per-family launch times -> dominant family
-        nb = len(fl)
-        prof = Profiler(L, args.steps * (2 + 4 * nb), (1 << len(native.KIND_NAMES)) - 1)
-        for _ in range(args.steps):
-            forward_profiled(model, x, y, prof)
-        torch.cuda.synchronize()
-        per_kind = {}
-        for kind, _, ms in prof.elapsed():
-            per_kind[kind] = per_kind.get(kind, 0.0) + ms
-        prof.close()
-        split_on = model.gc_arithmetic == "split"
-        fused_t = split_on and (T, V) in FUSED_TEMPORAL
-        fused_b = native.KIND_BLOCK in per_kind  # the blocks ran as single launches (k_block_fused)
-        if fused_b:
-            fl = merge_blocks(fl, fused_t)
-        dominant = max((k for k in per_kind if k in fl[0]), key=lambda k: per_kind[k])
-
-        # timed region: exactly K steps; in one of every P steps two events
-        # around the dominant family's launch in DSTDGCB 1 (an encoder) -- an
-        # event pair in every step slows the whole step by ~5%
+        prof = probe = None
         every = max(1, args.probe_every)
-        prof = Profiler(L, (args.steps + every - 1) // every, 1 << dominant)
-        prof.prof.only_block = 1
-        probe = ctypes.byref(prof.prof)
+        if args.full:
+            # untimed pass: per-family launch times -> dominant family
+            L = native.lib()
+            fl = model_block_flops(opts, split_on)
+            nb = len(fl)
+            prof = Profiler(L, args.steps * (2 + 4 * nb), (1 << len(native.KIND_NAMES)) - 1)
+            for _ in range(args.steps):
+                forward_profiled(model, x, y, prof)
+            torch.cuda.synchronize()
+            per_kind = {}
+            for kind, _, ms in prof.elapsed():
+                per_kind[kind] = per_kind.get(kind, 0.0) + ms
+            prof.close()
+            fused_t = split_on and (T, V) in FUSED_TEMPORAL
+            fused_b = native.KIND_BLOCK in per_kind  # the blocks ran as single launches (k_block_fused)
+            if fused_b:
+                fl = merge_blocks(fl, fused_t)
+            dominant = max((k for k in per_kind if k in fl[0]), key=lambda k: per_kind[k])
+
+            # in one of every P timed steps two events around the dominant
+            # family's launch in DSTDGCB 1 (an encoder) -- an event pair in
+            # every step slows the whole step by ~5%
+            prof = Profiler(L, (args.steps + every - 1) // every, 1 << dominant)
+            prof.prof.only_block = 1
+            probe = ctypes.byref(prof.prof)
+
+        # timed region: exactly K steps
         host_s = 0.0
         barrier()
         torch.cuda.synchronize()
@@ -578,7 +595,7 @@ def main():
         for i in range(args.steps):
             # the drop-in call itself (DSTDGCN.forward -> _forward_native -> the C
             # ABI); a probed step carries the event brackets through the module
-            if i % every == 0:
+            if probe is not None and i % every == 0:
                 model._dstd_profile = probe
             h0 = time.perf_counter()
             y = model(x)
@@ -587,8 +604,14 @@ def main():
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
-        launches = prof.elapsed()
-        prof.close()
+        if prof is not None:
+            launches = prof.elapsed()
+            prof.close()
+
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "y.npy" if world == 1 else f"y_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), y.detach().float().cpu().numpy())
 
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -597,27 +620,6 @@ def main():
         # metric exchange over RCCL after the timed region: output checksum
         # partials (the forward itself has no exchange)
         D.reduce_partials(y.double().abs().sum().reshape(1), torch.tensor([B], device=device))
-
-    bb = model_block_bytes(opts, split_on)
-    if fused_b:
-        bb = merge_blocks(bb, fused_t)
-    kernel_ms = sum(ms for _, _, ms in launches)
-    avg_launch_s = kernel_ms * 1e-3 / max(len(launches), 1)
-    C = opts["num_feature"]
-    # compulsory bytes of the probed launch: DSTDGCB 1 is a 64 -> 64 block; its
-    # spatial / temporal GC launch is one DSTDGC's input read + output write
-    comp = op_compulsory_bytes(C, C, T, V) * B
-    achieved = comp / avg_launch_s / 1e9 if kernel_ms > 0 else 0.0
-    kname = native.KIND_NAMES[dominant]
-    split_blk = split_on and opts["num_layers"] > 0
-    traffic = load_traffic(kname + "_split" if split_blk else kname, split_instance(dominant, T, V) if split_blk else None)
-    total_flop_per_seq = sum(sum(b.values()) for b in fl)
-    # algorithmic FLOPs of the probed launch (the fused temporal launch also
-    # builds its own adjacency and, phase 3, the next block's spatial one:
-    # those families' FLOPs count to it -- phase3_moves did the latter)
-    launch_flop = fl[1][dominant] + (fl[1][native.KIND_ADJ_T] if fused_t and dominant == native.KIND_TEMPORAL else 0)
-    flops = launch_flop * B / avg_launch_s / 1e12 if kernel_ms > 0 else 0.0
-    whole_bytes = model_compulsory_bytes(opts) * G * args.steps / elapsed / 1e9
 
     if rank == 0:
         out = {
@@ -642,49 +644,72 @@ def main():
             "config": {"workload": CONFIGS[args.config][1] + (f", {G} sequences over {world} GPU(s)" if strong else
                                                               f", B={B}/GPU") + ", eval forward",
                        "global_batch": G, "seq_len": T, "joints": V, "parallelism": f"dp{world}"},
-            "roofline": {"bound": "hbm", "kernel": kname + (" (split-f16, DSTDGCB 1)" if split_blk else " (DSTDGCB 1)"),
-                         "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                         "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": traffic,
-                         "compulsory_bytes_per_launch": comp,
-                         "compulsory_basis": f"SURVEY §8(d): {op_compulsory_bytes(C, C, T, V)} B/seq (" +
-                                             ("one 64->64 DSTDGCB, the launch's whole block" if fused_b else
-                                              "one 64->64 DSTDGC") +
-                                             f": input read + output written once) x {B} seq",
-                         "layout_bytes_per_launch": int(bb[1][dominant] * B) if launches else None,
-                         "launches": len(launches), "probe_every": every,
-                         "avg_launch_us": round(avg_launch_s * 1e6, 2),
-                         "compute": {"flop_per_launch": launch_flop * B, "achieved_tflops": round(flops, 2),
-                                     "frac_fp32_peak": round(flops / PEAK_FP32_TFLOPS, 4),
-                                     "frac_split_f16_ceiling": round(flops / (PEAK_F16_DENSE_TFLOPS / 3), 4),
-                                     "note": "fp32 FLOPs of the launch over the fp32 peak (157 TF, SURVEY §8(d)) and "
-                                             "over the split-f16 ceiling (dense f16 MFMA / 3 products)"},
-                         "whole_forward": {"compulsory_bytes_per_seq": model_compulsory_bytes(opts),
-                                           "achieved_gbs": round(whole_bytes, 1),
-                                           "frac_hbm": round(whole_bytes / PEAK_HBM_GBS, 4),
-                                           "flop_per_seq": total_flop_per_seq,
-                                           "achieved_tflops": round(total_flop_per_seq * G * args.steps / elapsed / 1e12,
-                                                                    3)}},
-            "kernel_ms_per_step_event_bracketed": {native.KIND_NAMES[k]: round(v / args.steps, 4)
-                                                   for k, v in sorted(per_kind.items())},
             "host_us_per_call": round(host_s / args.steps * 1e6, 2),
             "timed_call": "model(x): DSTDGCN.forward (the drop-in path) -> eager: DSTDGCN._forward_native -> "
                           "dstd_model_fwd_ex, the implementation of torch.ops.dstd.dstdgcn_forward without the "
                           "dispatcher's boxing (the op itself runs under tracing / torch.compile)",
         }
-        side_cpu = None if args.no_cpu_baseline else args.side_cpu_seconds
-        if world == 1 and args.config == "h36m" and not args.no_variant:
-            out["variant_t75"] = config_leg("h36m75", B, device, args.steps, args.warmup, side_cpu)
-            out["cmu_b256"] = config_leg("cmu", B, device, args.steps, args.warmup, side_cpu)
-            out["3dpw_b256"] = config_leg("3dpw", B, device, args.steps, args.warmup, side_cpu)
-        if world == 1 and not args.no_side:
-            out["exact_fp32"] = arithmetic_leg(model, x, "fp32", args.steps, args.warmup)
-            out["eval_b32"] = small_batch_leg(model, x, 32, max(args.steps, 100), args.warmup)
-            out["train_b32"] = train_leg(device, 32, 20, 5)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(opts, sd, x_cpu, args.cpu_seconds, 30.0)
-            out["vs_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
-        else:
-            out["cpu_baseline"] = None
+        out["full"] = args.full
+        if args.full:
+            bb = model_block_bytes(opts, split_on)
+            if fused_b:
+                bb = merge_blocks(bb, fused_t)
+            kernel_ms = sum(ms for _, _, ms in launches)
+            avg_launch_s = kernel_ms * 1e-3 / max(len(launches), 1)
+            C = opts["num_feature"]
+            # compulsory bytes of the probed launch: DSTDGCB 1 is a 64 -> 64 block; its
+            # spatial / temporal GC launch is one DSTDGC's input read + output write
+            comp = op_compulsory_bytes(C, C, T, V) * B
+            achieved = comp / avg_launch_s / 1e9 if kernel_ms > 0 else 0.0
+            kname = native.KIND_NAMES[dominant]
+            split_blk = split_on and opts["num_layers"] > 0
+            traffic = load_traffic(kname + "_split" if split_blk else kname, split_instance(dominant, T, V) if split_blk else None)
+            total_flop_per_seq = sum(sum(b.values()) for b in fl)
+            # algorithmic FLOPs of the probed launch (the fused temporal launch also
+            # builds its own adjacency and, phase 3, the next block's spatial one:
+            # those families' FLOPs count to it -- phase3_moves did the latter)
+            launch_flop = fl[1][dominant] + (fl[1][native.KIND_ADJ_T] if fused_t and dominant == native.KIND_TEMPORAL else 0)
+            flops = launch_flop * B / avg_launch_s / 1e12 if kernel_ms > 0 else 0.0
+            whole_bytes = model_compulsory_bytes(opts) * G * args.steps / elapsed / 1e9
+
+            out["roofline"] = {"bound": "hbm", "kernel": kname + (" (split-f16, DSTDGCB 1)" if split_blk else " (DSTDGCB 1)"),
+                               "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                               "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": traffic,
+                               "compulsory_bytes_per_launch": comp,
+                               "compulsory_basis": f"SURVEY §8(d): {op_compulsory_bytes(C, C, T, V)} B/seq (" +
+                                                   ("one 64->64 DSTDGCB, the launch's whole block" if fused_b else
+                                                    "one 64->64 DSTDGC") +
+                                                   f": input read + output written once) x {B} seq",
+                               "layout_bytes_per_launch": int(bb[1][dominant] * B) if launches else None,
+                               "launches": len(launches), "probe_every": every,
+                               "avg_launch_us": round(avg_launch_s * 1e6, 2),
+                               "compute": {"flop_per_launch": launch_flop * B, "achieved_tflops": round(flops, 2),
+                                           "frac_fp32_peak": round(flops / PEAK_FP32_TFLOPS, 4),
+                                           "frac_split_f16_ceiling": round(flops / (PEAK_F16_DENSE_TFLOPS / 3), 4),
+                                           "note": "fp32 FLOPs of the launch over the fp32 peak (157 TF, SURVEY §8(d)) and "
+                                                   "over the split-f16 ceiling (dense f16 MFMA / 3 products)"},
+                               "whole_forward": {"compulsory_bytes_per_seq": model_compulsory_bytes(opts),
+                                                 "achieved_gbs": round(whole_bytes, 1),
+                                                 "frac_hbm": round(whole_bytes / PEAK_HBM_GBS, 4),
+                                                 "flop_per_seq": total_flop_per_seq,
+                                                 "achieved_tflops": round(total_flop_per_seq * G * args.steps / elapsed / 1e12,
+                                                                          3)}}
+            out["kernel_ms_per_step_event_bracketed"] = {native.KIND_NAMES[k]: round(v / args.steps, 4)
+                                                         for k, v in sorted(per_kind.items())}
+            side_cpu = None if args.no_cpu_baseline else args.side_cpu_seconds
+            if world == 1 and args.config == "h36m" and not args.no_variant:
+                out["variant_t75"] = config_leg("h36m75", B, device, args.steps, args.warmup, side_cpu)
+                out["cmu_b256"] = config_leg("cmu", B, device, args.steps, args.warmup, side_cpu)
+                out["3dpw_b256"] = config_leg("3dpw", B, device, args.steps, args.warmup, side_cpu)
+            if world == 1 and not args.no_side:
+                out["exact_fp32"] = arithmetic_leg(model, x, "fp32", args.steps, args.warmup)
+                out["eval_b32"] = small_batch_leg(model, x, 32, max(args.steps, 100), args.warmup)
+                out["train_b32"] = train_leg(device, 32, 20, 5)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(opts, sd, x_cpu, args.cpu_seconds, 30.0)
+                out["vs_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -15,6 +15,8 @@ st=$?; echo "smoke exit $st"; tail -3 gpurun_out/smoke.log
 [ $st -eq 0 ] || ok_status $st || exit $st
 
 if [ -n "${BENCH_ARGS+x}" ] || [ -z "${NO_BENCH:-}" ]; then
+  # the default is the whole line (side legs, roofline, CPU baselines): --full
+  [ -n "${BENCH_ARGS:-}" ] || BENCH_ARGS="--full --steps 10 --warmup 3 --cpu-seconds 5"
   timeout -k 10 600 python bench.py ${BENCH_ARGS:---steps 10 --warmup 3 --cpu-seconds 5} > gpurun_out/bench.log 2>&1
   st=$?; echo "bench exit $st"; tail -5 gpurun_out/bench.log
 fi
