@@ -14,18 +14,6 @@
 
 using namespace dstd;
 
-#ifdef DSTD_SPRE_CHECK
-#include <stdio.h>
-// (debug builds: the planes phase 3 left in adj_s against a k_adj_hl<0> run
-// of the same block into a private buffer -- mismatching halves and the first)
-__global__ void k_cmp_u16(const uint16_t* a, const uint16_t* b, size_t n, unsigned* out) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    if (a[i] != b[i]) {
-      atomicAdd(&out[0], 1u);
-      atomicMin(&out[1], (unsigned)i);
-    }
-}
-#endif
 namespace {
 
 constexpr int kMaxT = 128;  // the generic kernels cover T <= 128 (adjacency row groups past 112)
@@ -285,13 +273,11 @@ BlockHL block_hl(const dstd_block_params* p, const BlockTail& tail, int B, int T
         ((p->cout == 64 && (tail.epi == TEPI_ENC || tail.epi == TEPI_IN || tail.epi == TEPI_RAW) &&
           (!tail.next || tail.next->cin == 64)) ||
          (p->cout == 3 && (tail.epi == TEPI_OUT || tail.epi == TEPI_RAW) && !tail.next));
-#ifndef DSTD_NO_TFUSED
   // one workgroup per sample: below one sample per CU the fused kernel leaves
   // CUs idle and the unit-parallel pair (k_adj_hl<1> + k_temporal_hl) wins
   // (B = 16..128: 25-30% faster forward; B = 256: 8% slower, profiles/r03m_small_batch_ab.txt)
   r.tf = r.t && temporal_fused_supported(T, V) &&
          ((B >= hl_device_cus() && temporal_fused_default(T, V)) || (flags & DSTD_FWD_FUSED_TEMPORAL));
-#endif
   // the whole block as one launch wherever both GCs run split and the
   // temporal one fused (one workgroup per sample either way)
   r.bf = r.s && r.tf && !(flags & DSTD_FWD_SEPARATE_BLOCK) && block_fused_supported(T, V, p->cin, p->cout, tail.epi);
@@ -402,37 +388,6 @@ hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const Block
     }
     // (s_pre: already in sc.adj_s, built by the previous block's temporal launch)
     if (adj_launch) e = launch_adj_hl(ah, 0, T, V, s);
-#ifdef DSTD_SPRE_CHECK
-    if (hl.s_pre) {
-      const size_t n = (size_t)2 * adj_s_floats(B, T, V);  // halves
-      uint16_t* ref = nullptr;
-      unsigned* cnt = nullptr;
-      (void)hipMalloc(&ref, n * 2);
-      (void)hipMalloc(&cnt, 8);
-      const unsigned init[2] = {0u, 0xffffffffu};
-      (void)hipMemcpy(cnt, init, 8, hipMemcpyHostToDevice);
-      AdjHLArgs ac = ah;
-      ac.out = ref;
-      (void)hipStreamSynchronize(s);
-      (void)launch_adj_hl(ac, 0, T, V, s);
-      hipLaunchKernelGGL(k_cmp_u16, dim3(1024), dim3(256), 0, s, reinterpret_cast<const uint16_t*>(sc.adj_s), ref,
-                         (size_t)B * ah.out_sN, cnt);
-      unsigned h[2];
-      (void)hipMemcpy(h, cnt, 8, hipMemcpyDeviceToHost);
-      uint16_t va = 0, vb = 0;
-      if (h[0]) {
-        (void)hipMemcpy(&va, reinterpret_cast<const uint16_t*>(sc.adj_s) + h[1], 2, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(&vb, ref + h[1], 2, hipMemcpyDeviceToHost);
-      }
-      const long i = h[1], per_n = ah.out_sN, per_g = ah.out_sG, ncol = V * hl_sl_spatial(V);
-      fprintf(stderr, "spre check cin %d cout %d: %u of %ld halves differ; first %ld (n %ld g %ld t %ld plane %ld col %ld) %04x vs %04x\n",
-              p->cin, p->cout, h[0], (long)B * per_n, h[0] ? i : -1L, h[0] ? i / per_n : -1L,
-              h[0] ? i % per_n / per_g : -1L, h[0] ? i % per_g / (2 * ncol) : -1L,
-              h[0] ? i % (2 * ncol) / ncol : -1L, h[0] ? i % ncol : -1L, va, vb);
-      (void)hipFree(ref);
-      (void)hipFree(cnt);
-    }
-#endif
   } else {
     e = launch_adj(aa, s);
   }
@@ -1014,7 +969,6 @@ int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* 
     hls[b] = block_hl(blk[b], tails[b], B, T, V, flags);
     add_block_hl_jobs(hj, blk[b], *fold[b], tails[b], hls[b], T, V);
   }
-#ifndef DSTD_NO_SPRE
   // a block's spatial adjacency from the previous block's fused temporal
   // launch (phase 3), which writes the P/Q it is built from
   for (int b = 1; b < NB && !(flags & DSTD_FWD_SEPARATE_ADJ); ++b)
@@ -1023,7 +977,6 @@ int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* 
       tails[b - 1].next_f = fold[b];
       tails[b - 1].next_adj = true;
     }
-#endif
   // block 0's spatial planes (from the model input) inside its block launch
   // rather than a k_adj_hl<0> launch of their own
   if (hls[0].bf && !(flags & DSTD_FWD_SEPARATE_ADJ) && blk[0]->cin == 6 && block_fused_adj0_supported(T, V))

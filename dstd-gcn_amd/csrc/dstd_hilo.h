@@ -52,14 +52,6 @@ __device__ __forceinline__ void split8(const float4& a, const float4& b, uint4& 
   hi.y = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a.z, a.w}, f16x2_t));
   hi.z = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){b.x, b.y}, f16x2_t));
   hi.w = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){b.z, b.w}, f16x2_t));
-#ifdef DSTD_SPLIT_CVT
-  const f16x2_t h0 = __builtin_bit_cast(f16x2_t, hi.x), h1 = __builtin_bit_cast(f16x2_t, hi.y);
-  const f16x2_t h2 = __builtin_bit_cast(f16x2_t, hi.z), h3 = __builtin_bit_cast(f16x2_t, hi.w);
-  lo.x = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a.x - (float)h0[0], a.y - (float)h0[1]}, f16x2_t));
-  lo.y = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a.z - (float)h1[0], a.w - (float)h1[1]}, f16x2_t));
-  lo.z = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){b.x - (float)h2[0], b.y - (float)h2[1]}, f16x2_t));
-  lo.w = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){b.z - (float)h3[0], b.w - (float)h3[1]}, f16x2_t));
-#else
   asm("v_fma_mixlo_f16 %0, %4, 1.0, -%12 op_sel_hi:[0,0,1]\n\t"
       "v_fma_mixhi_f16 %0, %5, 1.0, -%12 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
       "v_fma_mixlo_f16 %1, %6, 1.0, -%13 op_sel_hi:[0,0,1]\n\t"
@@ -72,7 +64,6 @@ __device__ __forceinline__ void split8(const float4& a, const float4& b, uint4& 
       : "=&v"(lo.x), "=&v"(lo.y), "=&v"(lo.z), "=&v"(lo.w)
       : "v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w), "v"(hi.x), "v"(hi.y),
         "v"(hi.z), "v"(hi.w));
-#endif
 }
 __device__ __forceinline__ void split8(const float4& a, const float4& b, f16x8& hi, f16x8& lo) {
   uint4 h, l;
@@ -236,43 +227,22 @@ __host__ __device__ constexpr inline int hl_rm_tail(int K) { return K % 32 != 0 
 __host__ __device__ constexpr inline int hl_rm_kp(int K) { return 32 * hl_rm_nsf(K) + 16 * hl_rm_tail(K); }
 
 // Row placement of the E / F arrays of the tanh GEMMs (k_adj_hl, phases 1 and
-// 3 of k_temporal_fused): row r starts at float r * SE + 4 * (((r >> SH) & MSK)
-// * MUL).  A lane of the tanh fragments reads 16 bytes of row pr (E) and qr
-// (F) at k = 32 s + 8 kg (+ 4); in the slot order of the planes the 16 lanes
-// of one ds_read_b128 bank group read rows whose plain-stride starts collide
-// on the 64 banks (2-3 extra LDS cycles per read).  -DDSTD_EF_SWIZZLE places
-// the rows by offsets chosen per shape with a bank model of the access (the
-// guide's ds_read_b128 lane groups; rows disjoint and 16-byte aligned): the
-// fused temporal kernel's bank-conflict cycles fell 1.041e6 -> 6.37e5 per
-// launch, bit-identical, but the forward got 0.7% slower at H36M (the row
-// offsets cost VALU in a kernel that is issue-bound, not LDS-bound:
-// profiles/r05h_lds_layout_ab.txt), so the plain stride stays the default.
-template <int SE_, int SH = 0, int MSK = 0, int MUL = 0>
+// 3 of k_temporal_fused) for contraction length K: row r starts at float
+// r * SE, SE = the padded K + 4.  A lane of the tanh fragments reads 16 bytes
+// of row pr (E) and qr (F) at k = 32 s + 8 kg (+ 4); in the slot order of the
+// planes the 16 lanes of one ds_read_b128 bank group read rows whose starts
+// collide on the 64 banks (2-3 extra LDS cycles per read).  Row offsets chosen
+// per shape with a bank model of the access took the fused temporal kernel's
+// bank-conflict cycles 1.041e6 -> 6.37e5 per launch, bit-identical, but the
+// forward got 0.7% slower at H36M (the offsets cost VALU in a kernel that is
+// issue-bound, not LDS-bound: profiles/r05h_lds_layout_ab.txt; the placements
+// tried: DESIGN.md section 4), so the plain stride stays.
+template <int K>
 struct EfRows {
-  static constexpr int SE = SE_;
-  __host__ __device__ static constexpr int row(int r) { return r * SE + 4 * (((r >> SH) & MSK) * MUL); }
+  static constexpr int SE = hl_rm_kp(K) + 4;
+  __host__ __device__ static constexpr int row(int r) { return r * SE; }
   __host__ __device__ static constexpr int floats(int nrows) { return row(nrows - 1) + SE; }
 };
-// TEMPORAL: rows = frames (NA = T slots, K = 2V); spatial: rows = joints (NA =
-// V, K = 2T).  Modelled extra LDS cycles per tile set (E and F reads) in the
-// comments: plain KP + 4 stride -> this placement.
-#ifdef DSTD_EF_SWIZZLE  // (off: measured slower, DESIGN.md section 4 "LDS bank conflicts")
-template <bool TEMPORAL, int NA, int K>
-struct EfPick {
-  using type = EfRows<hl_rm_kp(K) + 4>;
-};
-template <> struct EfPick<true, 35, 44> { using type = EfRows<72, 0, 1, 5>; };    // H36M temporal: 1044 -> 484
-template <> struct EfPick<false, 22, 70> { using type = EfRows<88, 0, 1, 1>; };   // H36M spatial: 660 -> 132
-template <> struct EfPick<true, 40, 46> { using type = EfRows<56, 0, 1, 1>; };    // 3DPW temporal: 1200 -> 800
-template <> struct EfPick<false, 23, 80> { using type = EfRows<88, 0, 1, 1>; };   // 3DPW spatial: 692 -> 140
-template <> struct EfPick<true, 35, 50> { using type = EfRows<72, 0, 1, 1>; };    // CMU temporal: 1808 -> 272
-template <> struct EfPick<false, 25, 70> { using type = EfRows<112, 3, 1, 1>; };  // CMU spatial: 800 -> 200
-#else  // the plain KP + 4 stride
-template <bool TEMPORAL, int NA, int K>
-struct EfPick {
-  using type = EfRows<hl_rm_kp(K) + 4>;
-};
-#endif
 enum HLJobKind { HLJ_CONV = 0, HLJ_PQ = 1, HLJ_RM = 2 };
 struct HLJob {
   int kind;

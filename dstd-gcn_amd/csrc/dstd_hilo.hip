@@ -29,18 +29,6 @@
 // Workgroup timeline of the split adjacency kernel (debug builds,
 // -DDSTD_STAMPS; scripts/timeline.py --hl): s_memrealtime at entry, prologue
 // done, tiles done, exit.
-#ifdef DSTD_TF_DUMPP
-__device__ unsigned g_dbg_planes[64 * 1024];
-extern "C" int dstd_debug_planes(unsigned* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_dbg_planes), sizeof(g_dbg_planes), 0);
-}
-#endif
-#ifdef DSTD_TF_DEBUGW
-__device__ unsigned g_dbg_w[2 * 512 * 24];
-extern "C" int dstd_debug_w(unsigned* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_dbg_w), sizeof(g_dbg_w), 0);
-}
-#endif
 #ifdef DSTD_STAMPS
 // modes: 0 k_adj_hl<0>, 1 k_adj_hl<1>, 2 k_temporal_fused phase 3 (start,
 // E/F ready, tiles issued, stores drained), 3 k_temporal_fused C = 64 (entry,
@@ -63,12 +51,7 @@ __device__ __forceinline__ f16x8 as_h8(const uint4& v) { return __builtin_bit_ca
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f32x4 mfma32(const f16x8& a, const f16x8& b, f32x4 c) {
-#ifdef DSTD_ABL_MFMA
-  c[0] += (float)a[0] * (float)b[0];
-  return c;
-#else
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-#endif
 }
 
 // hi/lo pair of an f32x4 quartet from two accumulator tiles (slots e = 0..3
@@ -114,18 +97,12 @@ constexpr uint32_t OOB = 0x80000000u;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, uint32_t bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
 }
-template <int AUX = 0>
+// (plain cache policy on every load; nt / sc bits on the temporal units'
+// h-row and residual loads, their last read, were tried: DESIGN.md section 4)
 __device__ __forceinline__ float4 bld4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-#ifdef DSTD_ABL_LOAD
-  const float f = (float)(off & 255) * 1e-3f;
-  return make_float4(f, f, f, f);
-#endif
-  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, AUX));
+  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
 __device__ __forceinline__ uint4 bldu4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-#ifdef DSTD_ABL_LOAD
-  return make_uint4(off & 0x3c003c00u, off, off, off);
-#endif
   return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
 // cache policy of the activation / P-Q stores (GC kernels) and of the
@@ -134,27 +111,10 @@ __device__ __forceinline__ uint4 bldu4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
 // XCDs anyway, and no dirty L2 lines are left for the kernel boundary to
 // write back (forward 2% faster; sc1 on the adjacency planes measured 3%
 // slower, nt 30% slower -- scripts/ab_kernels.py)
-#ifndef DSTD_GC_ST_AUX
-#define DSTD_GC_ST_AUX 16
-#endif
-#ifndef DSTD_ADJ_ST_AUX
-#define DSTD_ADJ_ST_AUX 0
-#endif
-// (experiments: cache policy of the temporal units' h-row loads and of the
-// encoder residual loads -- both the last read of those rows)
-#ifndef DSTD_TF_H_LD_AUX
-#define DSTD_TF_H_LD_AUX 0
-#endif
-#ifndef DSTD_TF_R_LD_AUX
-#define DSTD_TF_R_LD_AUX 0
-#endif
-template <int AUX = DSTD_GC_ST_AUX>
+constexpr int kGcStAux = 16;
+constexpr int kAdjStAux = 0;
 __device__ __forceinline__ void bst4(__amdgpu_buffer_rsrc_t r, uint32_t off, float4 v) {
-#ifdef DSTD_ABL_STORE
-  if (v.x == 12345.f) off = 0;  // keep the value alive; store only lanes with nothing to store
-  else off = OOB;
-#endif
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, AUX);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, kGcStAux);
 }
 
 // ---- range scaling helpers (dstd_hilo.h "range scaling") ----
@@ -331,18 +291,13 @@ __global__ __launch_bounds__(256) void k_hl_prep(HLPrepArgs a) {
 //   6 -> 64 and conv_st_out 64 -> 3, :117-121), computed in output layout
 //   (A = W_r fragments, B = x rows of the output joints).
 // ===========================================================================
-#ifndef DSTD_HL_WPE
-#define DSTD_HL_WPE 2
-#endif
+// waves per SIMD of k_spatial_hl (3 needs the late residual of spatial_units
+// to fit its registers and measured 3-5% slower: DESIGN.md section 4)
+constexpr int kSpatialWavesPerSimd = 2;
 // threads per workgroup: one workgroup of 4 x (waves per SIMD) waves per CU,
 // so a CU stages one copy of the weight images (A/B against two 4-wave
 // workgroups: forward -2.3%)
-constexpr int spatial_nt() { return 64 * 4 * DSTD_HL_WPE; }
-// identity residual loaded after the aggregations (see spatial_units)
-#ifndef DSTD_SP_LATE_RES
-#define DSTD_SP_LATE_RES (DSTD_HL_WPE > 2)
-#endif
-constexpr bool kSpLateRes = DSTD_SP_LATE_RES;
+constexpr int spatial_nt() { return 64 * 4 * kSpatialWavesPerSimd; }
 
 // 8 consecutive channels k0 .. k0+7 of row `row` of a unit (C channels per
 // row, zero past C; C % 8 == 0 or C == 6 / 3)
@@ -487,8 +442,7 @@ __device__ __forceinline__ void stage_spatial(const SpatialHLArgs& a, SpatialSta
 struct NoPQSink {
   __device__ int operator()(int, int, float, float, float, float) const { return 0; }
 };
-template <int V, int CIN, int COUT, typename AdjLoad, bool LATE_RES = kSpLateRes, int ST_AUX = DSTD_GC_ST_AUX,
-          typename PQSink = NoPQSink>
+template <int V, int CIN, int COUT, typename AdjLoad, bool LATE_RES = false, typename PQSink = NoPQSink>
 __device__ __forceinline__ int spatial_units(const SpatialHLArgs& a, const SpatialStage<V, CIN, COUT>& st, int u,
                                              int uend, int ustep, AdjLoad load_adj_g, PQSink pq_sink = {}) {
   int bad = 0;
@@ -662,7 +616,7 @@ __device__ __forceinline__ int spatial_units(const SpatialHLArgs& a, const Spati
         for (int wt = 0; wt < NWT; ++wt) O[ct][wt] = mfma32(dh[ct], as_h8(ab[g][wt][0]), O[ct][wt]);
     }
 
-    // the identity residual after the aggregations (kSpLateRes: its 32
+    // the identity residual after the aggregations (LATE_RES: its 32
     // registers are not live through the convs; the frame was just read, so
     // the rows come from the cache)
     if constexpr (!RES && LATE_RES) {
@@ -742,7 +696,7 @@ __device__ __forceinline__ int spatial_units(const SpatialHLArgs& a, const Spati
         o[2] = prelu_m(fmaf(o[2], sc.z, sh.z) + r[2], pw, pc);
         o[3] = prelu_m(fmaf(o[3], sc.w, sh.w) + r[3], pw, pc);
         if constexpr (COUT % 4 == 0) {
-          bst4<ST_AUX>(ry, (uint32_t)((16 * wt + cl) * COUT + 16 * ct + 4 * kl) * 4, make_float4(o[0], o[1], o[2], o[3]));
+          bst4(ry, (uint32_t)((16 * wt + cl) * COUT + 16 * ct + 4 * kl) * 4, make_float4(o[0], o[1], o[2], o[3]));
         } else {
           static_assert(COUT == 3, "thin output: 3 channels");
           const uint32_t off = kl == 0 ? (uint32_t)(16 * wt + cl) * 12 : OOB;
@@ -751,7 +705,7 @@ __device__ __forceinline__ int spatial_units(const SpatialHLArgs& a, const Spati
           typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
           typedef float f32x3 __attribute__((ext_vector_type(3)));
           const f32x3 o3 = {o[0], o[1], o[2]};
-          __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(u32x3, o3), ry, off, 0, DSTD_GC_ST_AUX);
+          __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(u32x3, o3), ry, off, 0, kGcStAux);
         }
       }
     }
@@ -797,7 +751,7 @@ __device__ __forceinline__ int spatial_units(const SpatialHLArgs& a, const Spati
       for (int wt = 0; wt < NWT; ++wt) {
         const float4 pq4 = make_float4(fmaf(acc[wt][0], s, st.bql[0]), fmaf(acc[wt][1], s, st.bql[1]),
                                        fmaf(acc[wt][2], s, st.bql[2]), fmaf(acc[wt][3], s, st.bql[3]));
-        bst4<ST_AUX>(rp, wpq0 + wt * 256, pq4);
+        bst4(rp, wpq0 + wt * 256, pq4);
         if constexpr (!std::is_same<PQSink, NoPQSink>::value) {
           if (kl == 0 && 16 * wt + cl < V) bad |= pq_sink(u, 16 * wt + cl, pq4.x, pq4.y, pq4.z, pq4.w);
         }
@@ -809,7 +763,7 @@ __device__ __forceinline__ int spatial_units(const SpatialHLArgs& a, const Spati
 }
 
 template <int V, int CIN, int COUT>
-__global__ __launch_bounds__(spatial_nt()) __attribute__((amdgpu_waves_per_eu(DSTD_HL_WPE, DSTD_HL_WPE))) void k_spatial_hl(
+__global__ __launch_bounds__(spatial_nt()) __attribute__((amdgpu_waves_per_eu(kSpatialWavesPerSimd, kSpatialWavesPerSimd))) void k_spatial_hl(
     SpatialHLArgs a) {
   using SM = SlotMap<V, true>;
   constexpr int SL = SM::SL, NG = SM::NG, NWT = cdiv(V, 16);
@@ -820,11 +774,7 @@ __global__ __launch_bounds__(spatial_nt()) __attribute__((amdgpu_waves_per_eu(DS
   // arbitration losers at equal priority; MI355X guide "two waves per SIMD"
   // item 4, T5 static form): spatial GC -1.8%, forward -0.8% at H36M and
   // -0.9% at 3DPW, B=32 neutral, bit-identical (profiles/r05o_setprio_ab.txt)
-#ifndef DSTD_SETPRIO_SP  // (0: off)
-#define DSTD_SETPRIO_SP 256
-#endif
-  if (DSTD_SETPRIO_SP > 0 && __builtin_amdgcn_readfirstlane(threadIdx.x) >= DSTD_SETPRIO_SP)
-    __builtin_amdgcn_s_setprio(1);
+  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
   const int lane = threadIdx.x & 63, kl = lane >> 4, cl = lane & 15;
   const int T = a.T;
   constexpr uint32_t adj_bytes = 2 * V * SL * 2;  // one (n, g, t) adjacency: 2 planes of V x SL halves
@@ -859,9 +809,6 @@ __global__ __launch_bounds__(spatial_nt()) __attribute__((amdgpu_waves_per_eu(DS
 // tail is light enough for twice as many
 template <int T, int C>
 constexpr int temporal_hl_wpe() {
-#ifdef DSTD_T_WPE
-  return DSTD_T_WPE * (C == 3 ? 2 : 1);
-#endif
   return (T <= 48 || C == 64 ? 2 : 1) * (C == 3 ? 2 : 1);
 }
 // one workgroup per CU at the kernel's waves per SIMD (4 waves at one per
@@ -873,11 +820,11 @@ constexpr int temporal_nt() {
 
 // 8 channels k0 .. k0+7 of the row at byte offset `row_off` (C per row; zero
 // past C, and an out-of-range row_off reads zeros)
-template <int C, int AUX = 0>
+template <int C>
 __device__ __forceinline__ void load_row8_at(__amdgpu_buffer_rsrc_t r, uint32_t row_off, int k0, float4& lo4, float4& hi4) {
   if constexpr (C % 8 == 0) {
-    lo4 = bld4<AUX>(r, row_off + 4 * k0);
-    hi4 = bld4<AUX>(r, row_off + 4 * k0 + 16);
+    lo4 = bld4(r, row_off + 4 * k0);
+    hi4 = bld4(r, row_off + 4 * k0 + 16);
   } else {
     const uint32_t off = k0 == 0 ? row_off : OOB;
     float e[8];
@@ -911,9 +858,6 @@ struct TemporalStage {
 // the fused temporal body issues the loads before the barrier that ends
 // phase 1 (the tile registers are dead by then) and writes once the phase-1
 // scratch is free, so the load latency hides in the barrier wait.
-#ifndef DSTD_TF_STAGE_EARLY
-#define DSTD_TF_STAGE_EARLY 1
-#endif
 template <int T, int EPI, int C, int VB, int NTH>
 struct TemporalStageLoad {
   using S = TemporalStage<T, EPI, C, VB>;
@@ -1009,12 +953,6 @@ __device__ __forceinline__ void stage_temporal(const TemporalHLArgs& a, Temporal
 // HBM, k_temporal_hl: the loads fly during the conv); LAZY = true,
 // load_adj(u, s, bh[NUT], bo[NUT]) per aggregation K-step (the planes in LDS,
 // k_temporal_fused: 24 fewer live VGPRs).
-#ifndef DSTD_TF_LATE_RES
-#define DSTD_TF_LATE_RES 1
-#endif
-#ifndef DSTD_TF_RES_ACC
-#define DSTD_TF_RES_ACC 1
-#endif
 // shapes whose ENC units take the residual as the accumulator's initial
 // value: CMU (T 35, V 25; -2.8% per forward) and 3DPW (T 40, V 23; -2.3%, and
 // its 8-wave fused kernel fits 256 VGPRs without its 4 spills); not H36M
@@ -1072,7 +1010,7 @@ __device__ __forceinline__ void temporal_units(const TemporalHLArgs& a, const Te
     for (int m = 0; m < MT; ++m)
 #pragma unroll
       for (int ks = 0; ks < KSI; ++ks)
-        load_row8_at<C, DSTD_TF_H_LD_AUX>(r, xoff[m], 32 * ks + 8 * kl, xr[m][ks][0], xr[m][ks][1]);
+        load_row8_at<C>(r, xoff[m], 32 * ks + 8 * kl, xr[m][ks][0], xr[m][ks][1]);
   };
   if (PF && u < uend) load_x(u);
   while (u < uend) {
@@ -1158,16 +1096,16 @@ __device__ __forceinline__ void temporal_units(const TemporalHLArgs& a, const Te
 #pragma unroll
       for (int ut = 0; ut < NUTC; ++ut)
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) R[ct][ut] = bld4<DSTD_TF_R_LD_AUX>(rr, uoff[ut] + 64 * ct);
+        for (int ct = 0; ct < NCT; ++ct) R[ct][ut] = bld4(rr, uoff[ut] + 64 * ct);
     };
-    constexpr bool late_res = LAZY && DSTD_TF_LATE_RES;
+    constexpr bool late_res = LAZY;
     // RES_ACC: the ENC residual is the aggregation accumulator's initial
     // value (scaled like the sum, 2^-(sx+sa)) -- the MFMAs add it, the
     // epilogue does not (48 VALU adds per unit), and it needs no registers of
     // its own across the aggregation.  Chosen per shape by the kernels
     // (tf_res_acc, the same for the fused and unfused schedules of a shape so
     // they stay bit-identical)
-    constexpr bool res_acc = EPI == TEPI_ENC && DSTD_TF_RES_ACC && RA;
+    constexpr bool res_acc = EPI == TEPI_ENC && RA;
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (EPI == TEPI_ENC && !late_res && !res_acc) {
       load_res_enc();
@@ -1191,7 +1129,7 @@ __device__ __forceinline__ void temporal_units(const TemporalHLArgs& a, const Te
       for (int ut = 0; ut < NUTC; ++ut)
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {
-          const float4 r4 = bld4<DSTD_TF_R_LD_AUX>(rr, uoff[ut] + 64 * ct);
+          const float4 r4 = bld4(rr, uoff[ut] + 64 * ct);
           O[ct][ut] = f32x4{r4.x, r4.y, r4.z, r4.w};
         }
       if (const int su0 = min(sx + sa, 127)) {
@@ -1316,7 +1254,7 @@ __device__ __forceinline__ void temporal_units(const TemporalHLArgs& a, const Te
           typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
           typedef float f32x3 __attribute__((ext_vector_type(3)));
           const f32x3 o3 = {o[0], o[1], o[2]};
-          __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(u32x3, o3), ry, uoff[ut], 0, DSTD_GC_ST_AUX);
+          __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(u32x3, o3), ry, uoff[ut], 0, kGcStAux);
         }
       }
     }
@@ -1403,9 +1341,6 @@ __global__ __launch_bounds__((temporal_nt<T, C>())) __attribute__((amdgpu_waves_
   __shared__ TemporalStage<T, EPI, C, 32> st;
   stage_temporal<T, EPI, C, 32, temporal_nt<T, C>()>(a, st, threadIdx.x);
   __syncthreads();
-#ifdef DSTD_SETPRIO_TH  // (experiment: the younger waves' static priority, as k_spatial_hl)
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= DSTD_SETPRIO_TH) __builtin_amdgcn_s_setprio(1);
-#endif
   int uend;
   const int u0 = unit_range(a.B * a.V, uend);
   const int cl = threadIdx.x & 15, kl = (threadIdx.x & 63) >> 4;
@@ -1473,12 +1408,6 @@ __device__ __forceinline__ void tanh_run(const float* ep, const float* fq, float
     ev[h] = e.x, ev[h + 1] = e.y, ev[h + 2] = e.z, ev[h + 3] = e.w;
     fv[h] = f.x, fv[h + 1] = f.y, fv[h + 2] = f.z, fv[h + 3] = f.w;
   }
-#ifdef DSTD_TANH_SCALAR
-  if constexpr (SEP) {
-#pragma unroll
-    for (int e = 0; e < N; ++e) tv[e] = fmaf(__builtin_amdgcn_rcpf(fmaf(ev[e], fv[e], 1.f)), -2.f, 1.f);
-  } else
-#endif
   if constexpr (SEP) {
 #pragma unroll
     for (int e2 = 0; e2 < N; e2 += 2) {  // E F + 1 and 1 - 2 r as packed fp32 (v_pk_fma_f32)
@@ -1571,16 +1500,14 @@ struct AdjHLGeom {
   static constexpr int NS = hl_rm_nsf(K), TAIL = hl_rm_tail(K), KP = 32 * NS + 16 * TAIL;
   static constexpr int RT = cdiv(NROW, 16), KH = K / 2;
   static constexpr int WIMG = RT * (NS * 2 * 64 + TAIL * 64);  // uint4 of the HLJ_RM image
-  using EF = typename EfPick<MODE == 1, NA, K>::type;  // E / F row placement
+  using EF = EfRows<K>;  // E / F row placement
   static constexpr int SE = EF::SE;
   using SM = SlotMap<NA, MODE == 0>;
   static constexpr int SL = SM::SL, NCOL = NA * SL, NCT = cdiv(NCOL, 16);
   // column chunks (one workgroup each) per (sample, graph) at full batch;
   // the launcher raises the count when B * ngroups * NCHUNK leaves CUs idle
-#ifndef DSTD_ADJ_T_NCHUNK  // (experiments: column chunks of the temporal adjacency per sample)
-#define DSTD_ADJ_T_NCHUNK 2
-#endif
-  static constexpr int NCHUNK = MODE == 0 ? 1 : DSTD_ADJ_T_NCHUNK;
+  // (temporal: other counts at T = 75, profiles/r06ab_t75_adj_chunks_ab.txt)
+  static constexpr int NCHUNK = MODE == 0 ? 1 : 2;
   static constexpr int CPC = cdiv(NCT, NCHUNK);
   static constexpr int OS = 20;  // staging row stride (floats)
   static constexpr int T = MODE == 0 ? NROW : NA, V = MODE == 0 ? NA : NROW;
@@ -1617,9 +1544,6 @@ __global__ __launch_bounds__((AdjHLGeom<MODE, NROW, K, NA>::AT)) void k_adj_hl(A
   const int n = blockIdx.x / (nch * a.ngroups);
   if (n >= a.B) return;
   TLH(MODE, 0)
-#ifdef DSTD_SETPRIO_ADJ  // (experiment: the younger waves' static priority, as k_spatial_hl)
-  if (__builtin_amdgcn_readfirstlane(tid) >= DSTD_SETPRIO_ADJ) __builtin_amdgcn_s_setprio(1);
-#endif
 
   // ---- prologue: P/Q -> E/F rows, conv_rm fragments, A-stat, bias.  Every
   // global load is issued before the first LDS write (one memory round
@@ -1790,8 +1714,8 @@ __global__ __launch_bounds__((AdjHLGeom<MODE, NROW, K, NA>::AT)) void k_adj_hl(A
         split8(v0, v1, hi, lo);
         // rows / columns past the plane: out-of-range offset, the store is dropped
         const uint32_t off = row < NROW && c8 < NCOL ? 2u * (uint32_t)(row * (2 * NCOL) + c8) : OOB;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), ro, off, 0, DSTD_ADJ_ST_AUX);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), ro, off + 2u * NCOL, 0, DSTD_ADJ_ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), ro, off, 0, kAdjStAux);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), ro, off + 2u * NCOL, 0, kAdjStAux);
       }
     }
   };
@@ -1835,7 +1759,7 @@ template <int T, int V, int EPI, int C>
 struct TFusedGeom {
   using SM = SlotMap<T, false>;
   static constexpr int K = 2 * V, NS = hl_rm_nsf(K), TAIL = hl_rm_tail(K), KP = 32 * NS + 16 * TAIL;
-  using EF = typename EfPick<true, T, K>::type;  // E / F row placement
+  using EF = EfRows<K>;  // E / F row placement
   static constexpr int SE = EF::SE, EFE = EF::floats(T + 1);  // floats of the E array (every input frame + pad row)
   static constexpr int SL = SM::SL, NUT = cdiv(T, 16);
   static constexpr int RTG = cdiv(V, 16);  // row tiles of the whole HLJ_RM image
@@ -1890,7 +1814,7 @@ template <int T, int V>
 struct SAdjGeom {
   using SM = SlotMap<V, true>;
   static constexpr int K = 2 * T, NS = hl_rm_nsf(K), TAIL = hl_rm_tail(K), KP = 32 * NS + 16 * TAIL;
-  using EF = typename EfPick<false, V, K>::type;  // E / F row placement
+  using EF = EfRows<K>;  // E / F row placement
   static constexpr int SE = EF::SE, EFN = EF::floats(V + 1);  // floats per E (F) array
   static constexpr int SL = SM::SL, NCOL = V * SL, NCTC = cdiv(NCOL, 16), RT = cdiv(T, 16), FULL = NS * 2 * 64;
   static constexpr int WIMG = RT * (FULL + TAIL * 64);  // uint4 of one graph's HLJ_RM image
@@ -1906,9 +1830,9 @@ struct SAdjGeom {
 };
 
 // The P/Q-independent global loads of spatial_adj_sample's prologue (both
-// conv_rm images, the Astat table entries, the conv_rm bias): issued by
-// phase 3's caller before the barrier that ends phase 2, so their latency
-// hides in the wait for the last joint units (the unit registers are dead)
+// conv_rm images, the Astat table entries, the conv_rm bias).  (Issued by
+// phase 3's caller before the barrier that ends phase 2 instead, to hide
+// their latency in that wait: 0.0% / -0.1% / +1.7%, r06q)
 template <int T, int V, int NT>
 struct SAdjStatic {
   using Gm = SAdjGeom<T, V>;
@@ -1940,11 +1864,9 @@ struct SAdjStatic {
 };
 
 // XIN: the P/Q from the model input (j.xin, conv_st_in's conv_m1/m2 rows
-// j.mw / j.mb, as k_adj_hl<0> forms them) instead of j.pq.  pre: the
-// prologue's static loads, already issued (SAdjStatic::load), or null
+// j.mw / j.mb, as k_adj_hl<0> forms them) instead of j.pq
 template <int T, int V, int NT, bool XIN = false>
-__device__ __forceinline__ void spatial_adj_sample(const AdjHLArgs& j, int n, unsigned char* dsm,
-                                                   const SAdjStatic<T, V, NT>* pre = nullptr) {
+__device__ __forceinline__ void spatial_adj_sample(const AdjHLArgs& j, int n, unsigned char* dsm) {
   using Gm = SAdjGeom<T, V>;
   using SM = typename Gm::SM;
   using EF = typename Gm::EF;
@@ -1962,7 +1884,7 @@ __device__ __forceinline__ void spatial_adj_sample(const AdjHLArgs& j, int n, un
   // ---- prologue: both graphs' P/Q -> E/F rows, conv_rm images, Astat, bias;
   // every global load before the first LDS write ----
   const PQLayout L = j.pql;
-  constexpr int NPQ = cdiv(T * V, NT), NWI = cdiv(2 * WIMG, NT), NAS = cdiv(2 * Gm::ASQ, NT);
+  constexpr int NPQ = cdiv(T * V, NT), NWI = SAdjStatic<T, V, NT>::NWI, NAS = SAdjStatic<T, V, NT>::NAS;
   auto pq_at = [&](int g, int i) __attribute__((always_inline)) -> float4 {  // (P_0, P_1, Q_0, Q_1) of element i (joint-major)
     const int t = i % T, v = i / T;
     return ld4(j.pq + (size_t)n * L.sn + j.p_ch[g] + t * L.st + v * L.sv);
@@ -2005,10 +1927,8 @@ __device__ __forceinline__ void spatial_adj_sample(const AdjHLArgs& j, int n, un
 #pragma unroll
       for (int it = 0; it < NPQ; ++it) q4[g][it] = pq_at(g, min(tid + it * NT, T * V - 1));
   }
-  static_assert(SAdjStatic<T, V, NT>::NWI == NWI && SAdjStatic<T, V, NT>::NAS == NAS, "prologue split");
   SAdjStatic<T, V, NT> sl;
-  if (pre) sl = *pre;
-  else sl.load(j, tid);
+  sl.load(j, tid);
   // planes stored as 2^-sa Adj, one sa for both graphs (dstd_hilo.h "range scaling")
   const float dna = pow2f(-hl_range_shift(
       fexp_bits(__float_as_uint(fmaxf(j.wscale[0][HLS_BOUND], j.wscale[1][HLS_BOUND])))));
@@ -2106,180 +2026,78 @@ __device__ __forceinline__ void spatial_adj_sample(const AdjHLArgs& j, int n, un
   const float inv0 = *j.wscale[0], inv1 = *j.wscale[1];
   TLH(2, 1)
 
-#ifndef DSTD_P3_TPI
-#define DSTD_P3_TPI 1
-#endif
-#ifndef DSTD_P3_NOSTORE  // (timing experiments only: the plane stores dropped, wrong output)
-#define DSTD_P3_NOSTORE 0
-#endif
-  constexpr int TPI = DSTD_P3_TPI;  // column tiles per iteration (independent dependency chains)
-  if constexpr (TPI == 1) {
-    // one tile space over both graphs (2 NCTC column tiles): the waves split
-    // it evenly instead of rounding up twice
-    f16x8 wh[RT][NS], wo[RT][NS];  // the current graph's conv_rm rows as B fragments
-    f16x4 wth[RT], wto[RT];        // (lane = row 16 rt + cl, k group kg)
-    float b[RT];
-    int gcur = -1;
+  // one tile space over both graphs (2 NCTC column tiles): the waves split
+  // it evenly instead of rounding up twice.  (One column tile per wave and
+  // trip; two interleaved chains per wave were measured, not kept:
+  // DESIGN.md section 4)
+  f16x8 wh[RT][NS], wo[RT][NS];  // the current graph's conv_rm rows as B fragments
+  f16x4 wth[RT], wto[RT];        // (lane = row 16 rt + cl, k group kg)
+  float b[RT];
+  int gcur = -1;
 #pragma unroll 1
-    for (int ti = wave; ti < 2 * NCTC; ti += NW) {
-      const int g = ti >= NCTC ? 1 : 0, ct = ti - g * NCTC;
-      if (g != gcur) {  // (wave-uniform: at most once per wave)
-        gcur = g;
-        const uint4* wg = wl + g * WIMG;
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-          for (int s = 0; s < NS; ++s) {
-            wh[rt][s] = as_h8(wg[((rt * NS + s) * 2 + 0) * 64 + lane]);
-            wo[rt][s] = as_h8(wg[((rt * NS + s) * 2 + 1) * 64 + lane]);
-          }
-          if constexpr (TAIL) {
-            const uint2* w16 = reinterpret_cast<const uint2*>(wg + RT * FULL);
-            wth[rt] = __builtin_bit_cast(f16x4, w16[(rt * 2 + 0) * 64 + lane]);
-            wto[rt] = __builtin_bit_cast(f16x4, w16[(rt * 2 + 1) * 64 + lane]);
-          }
-          b[rt] = bl[g * 16 * RT + 16 * rt + cl];
-        }
-      }
-      const float inv = g ? inv1 : inv0;
-      const float* El = Elg(g);
-      const float* Fl = El + EFN;
-      const float* as = asg(g);
-      const auto ro = rsrc(j.out + (size_t)n * j.out_sN + (size_t)g * j.out_sG, 2u * T * 2 * NCOL);
-      // this lane's A-operand row = column ct * 16 + cl of the planes
-      const int col = ct * 16 + cl;
-      const int qa = col / SL, pa = SM::slot_idx(col - qa * SL);
-      const bool va = col < NCOL && pa < V;
-      f16x8 bh[NS], bo[NS];
-      f16x4 th, to;
-      const int pb = EF::row(va ? pa : V), qb = EF::row(col < NCOL ? qa : V);
-      if (g ? sep1 : sep0) tanh_frags<true, NS, TAIL>(El, Fl, pb, qb, kg, bh, bo, th, to);
-      else tanh_frags<false, NS, TAIL>(El, Fl, pb, qb, kg, bh, bo, th, to);
-      // the accumulator's 4 columns colb .. colb + 3 (one joint q, slots slot0 ..)
-      const int colb = ct * 16 + 4 * kg;
-      const float4 as4 = ld4(as + colb), al4 = ld4(as + Gm::ASQ + colb);
-      const float asv[4] = {as4.x, as4.y, as4.z, as4.w}, al[4] = {al4.x, al4.y, al4.z, al4.w};
+  for (int ti = wave; ti < 2 * NCTC; ti += NW) {
+    const int g = ti >= NCTC ? 1 : 0, ct = ti - g * NCTC;
+    if (g != gcur) {  // (wave-uniform: at most once per wave)
+      gcur = g;
+      const uint4* wg = wl + g * WIMG;
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
-        f32x4 acc = zero4();
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          acc = mfma32(bh[s], wo[rt][s], acc);
-          acc = mfma32(bo[s], wh[rt][s], acc);
-          acc = mfma32(bh[s], wh[rt][s], acc);
+          wh[rt][s] = as_h8(wg[((rt * NS + s) * 2 + 0) * 64 + lane]);
+          wo[rt][s] = as_h8(wg[((rt * NS + s) * 2 + 1) * 64 + lane]);
         }
-        if constexpr (TAIL) {  // on an accumulator of its own (dstd_hilo.h: mixed-shape MFMA chains)
-          f32x4 tac = __builtin_amdgcn_mfma_f32_16x16x16f16(th, wto[rt], zero4(), 0, 0, 0);
-          tac = __builtin_amdgcn_mfma_f32_16x16x16f16(to, wth[rt], tac, 0, 0, 0);
-          tac = __builtin_amdgcn_mfma_f32_16x16x16f16(th, wth[rt], tac, 0, 0, 0);
-          acc += tac;
+        if constexpr (TAIL) {
+          const uint2* w16 = reinterpret_cast<const uint2*>(wg + RT * FULL);
+          wth[rt] = __builtin_bit_cast(f16x4, w16[(rt * 2 + 0) * 64 + lane]);
+          wto[rt] = __builtin_bit_cast(f16x4, w16[(rt * 2 + 1) * 64 + lane]);
         }
-        float vv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) vv[r] = fmaf(al[r], fmaf(acc[r], inv, b[rt]), asv[r]);
-        uint2 hi, lo;
-        split4(make_float4(vv[0], vv[1], vv[2], vv[3]), hi, lo);
-        // frame t = 16 rt + cl: the hi plane at [t][0][col], lo at [t][1][col]
-        const int t = 16 * rt + cl;
-        const uint32_t off = t < T && colb < NCOL && !DSTD_P3_NOSTORE ? 2u * (uint32_t)(t * 2 * NCOL + colb) : OOB;
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hi), ro, off, 0, DSTD_ADJ_ST_AUX);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lo), ro, off + 2u * NCOL, 0, DSTD_ADJ_ST_AUX);
+        b[rt] = bl[g * 16 * RT + 16 * rt + cl];
       }
     }
-  } else {
-    // TPI column tiles of ONE graph per task (the W fragments stay per
-    // graph): tasks = (graph, tile group), the waves split them evenly; a
-    // wave interleaves its tiles' tanh -> split -> MFMA chains (round 6:
-    // phase 3 ran ~3x over its issue bound at one chain per wave)
-    constexpr int NGRP = cdiv(NCTC, TPI);
-    f16x8 wh[RT][NS], wo[RT][NS];
-    f16x4 wth[RT], wto[RT];
-    float b[RT];
-    int gcur = -1;
-#pragma unroll 1
-    for (int ti = wave; ti < 2 * NGRP; ti += NW) {
-      const int g = ti >= NGRP ? 1 : 0, ct0 = (ti - g * NGRP) * TPI;
-      if (g != gcur) {  // (wave-uniform: at most once per wave)
-        gcur = g;
-        const uint4* wg = wl + g * WIMG;
+    const float inv = g ? inv1 : inv0;
+    const float* El = Elg(g);
+    const float* Fl = El + EFN;
+    const float* as = asg(g);
+    const auto ro = rsrc(j.out + (size_t)n * j.out_sN + (size_t)g * j.out_sG, 2u * T * 2 * NCOL);
+    // this lane's A-operand row = column ct * 16 + cl of the planes
+    const int col = ct * 16 + cl;
+    const int qa = col / SL, pa = SM::slot_idx(col - qa * SL);
+    const bool va = col < NCOL && pa < V;
+    f16x8 bh[NS], bo[NS];
+    f16x4 th, to;
+    const int pb = EF::row(va ? pa : V), qb = EF::row(col < NCOL ? qa : V);
+    if (g ? sep1 : sep0) tanh_frags<true, NS, TAIL>(El, Fl, pb, qb, kg, bh, bo, th, to);
+    else tanh_frags<false, NS, TAIL>(El, Fl, pb, qb, kg, bh, bo, th, to);
+    // the accumulator's 4 columns colb .. colb + 3 (one joint q, slots slot0 ..)
+    const int colb = ct * 16 + 4 * kg;
+    const float4 as4 = ld4(as + colb), al4 = ld4(as + Gm::ASQ + colb);
+    const float asv[4] = {as4.x, as4.y, as4.z, as4.w}, al[4] = {al4.x, al4.y, al4.z, al4.w};
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
+    for (int rt = 0; rt < RT; ++rt) {
+      f32x4 acc = zero4();
 #pragma unroll
-          for (int s = 0; s < NS; ++s) {
-            wh[rt][s] = as_h8(wg[((rt * NS + s) * 2 + 0) * 64 + lane]);
-            wo[rt][s] = as_h8(wg[((rt * NS + s) * 2 + 1) * 64 + lane]);
-          }
-          if constexpr (TAIL) {
-            const uint2* w16 = reinterpret_cast<const uint2*>(wg + RT * FULL);
-            wth[rt] = __builtin_bit_cast(f16x4, w16[(rt * 2 + 0) * 64 + lane]);
-            wto[rt] = __builtin_bit_cast(f16x4, w16[(rt * 2 + 1) * 64 + lane]);
-          }
-          b[rt] = bl[g * 16 * RT + 16 * rt + cl];
-        }
+      for (int s = 0; s < NS; ++s) {
+        acc = mfma32(bh[s], wo[rt][s], acc);
+        acc = mfma32(bo[s], wh[rt][s], acc);
+        acc = mfma32(bh[s], wh[rt][s], acc);
       }
-      const float inv = g ? inv1 : inv0;
-      const float* El = Elg(g);
-      const float* Fl = El + EFN;
-      const float* as = asg(g);
-      const auto ro = rsrc(j.out + (size_t)n * j.out_sN + (size_t)g * j.out_sG, 2u * T * 2 * NCOL);
-      const bool sepg = g ? sep1 : sep0;
-      f16x8 bh[TPI][NS], bo[TPI][NS];
-      f16x4 th[TPI], to[TPI];
-      float asv[TPI][4], al[TPI][4];
-      int colb[TPI];
-#pragma unroll
-      for (int i = 0; i < TPI; ++i) {
-        const int ct = ct0 + i;  // (past NCTC: padding columns, their stores dropped)
-        const int col = ct * 16 + cl;
-        const int qa = col / SL, pa = SM::slot_idx(col - qa * SL);
-        const bool va = col < NCOL && pa < V;
-        const int pb = EF::row(va ? pa : V), qb = EF::row(col < NCOL ? qa : V);
-        if (sepg) tanh_frags<true, NS, TAIL>(El, Fl, pb, qb, kg, bh[i], bo[i], th[i], to[i]);
-        else tanh_frags<false, NS, TAIL>(El, Fl, pb, qb, kg, bh[i], bo[i], th[i], to[i]);
-        colb[i] = ct * 16 + 4 * kg;
-        const int cb = min(colb[i], Gm::ASQ - 4);  // (padding tiles: any in-range table entry)
-        const float4 as4 = ld4(as + cb), al4 = ld4(as + Gm::ASQ + cb);
-        asv[i][0] = as4.x, asv[i][1] = as4.y, asv[i][2] = as4.z, asv[i][3] = as4.w;
-        al[i][0] = al4.x, al[i][1] = al4.y, al[i][2] = al4.z, al[i][3] = al4.w;
+      if constexpr (TAIL) {  // on an accumulator of its own (dstd_hilo.h: mixed-shape MFMA chains)
+        f32x4 tac = __builtin_amdgcn_mfma_f32_16x16x16f16(th, wto[rt], zero4(), 0, 0, 0);
+        tac = __builtin_amdgcn_mfma_f32_16x16x16f16(to, wth[rt], tac, 0, 0, 0);
+        tac = __builtin_amdgcn_mfma_f32_16x16x16f16(th, wth[rt], tac, 0, 0, 0);
+        acc += tac;
       }
+      float vv[4];
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        f32x4 acc[TPI];
-#pragma unroll
-        for (int i = 0; i < TPI; ++i) acc[i] = zero4();
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-#pragma unroll
-          for (int i = 0; i < TPI; ++i) acc[i] = mfma32(bh[i][s], wo[rt][s], acc[i]);
-#pragma unroll
-          for (int i = 0; i < TPI; ++i) acc[i] = mfma32(bo[i][s], wh[rt][s], acc[i]);
-#pragma unroll
-          for (int i = 0; i < TPI; ++i) acc[i] = mfma32(bh[i][s], wh[rt][s], acc[i]);
-        }
-        if constexpr (TAIL) {  // on accumulators of their own (dstd_hilo.h: mixed-shape MFMA chains)
-          f32x4 tac[TPI];
-#pragma unroll
-          for (int i = 0; i < TPI; ++i) tac[i] = __builtin_amdgcn_mfma_f32_16x16x16f16(th[i], wto[rt], zero4(), 0, 0, 0);
-#pragma unroll
-          for (int i = 0; i < TPI; ++i) tac[i] = __builtin_amdgcn_mfma_f32_16x16x16f16(to[i], wth[rt], tac[i], 0, 0, 0);
-#pragma unroll
-          for (int i = 0; i < TPI; ++i) tac[i] = __builtin_amdgcn_mfma_f32_16x16x16f16(th[i], wth[rt], tac[i], 0, 0, 0);
-#pragma unroll
-          for (int i = 0; i < TPI; ++i) acc[i] += tac[i];
-        }
-        const int t = 16 * rt + cl;
-#pragma unroll
-        for (int i = 0; i < TPI; ++i) {
-          float vv[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) vv[r] = fmaf(al[i][r], fmaf(acc[i][r], inv, b[rt]), asv[i][r]);
-          uint2 hi, lo;
-          split4(make_float4(vv[0], vv[1], vv[2], vv[3]), hi, lo);
-          const uint32_t off = t < T && colb[i] < NCOL ? 2u * (uint32_t)(t * 2 * NCOL + colb[i]) : OOB;
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hi), ro, off, 0, DSTD_ADJ_ST_AUX);
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lo), ro, off + 2u * NCOL, 0, DSTD_ADJ_ST_AUX);
-        }
-      }
+      for (int r = 0; r < 4; ++r) vv[r] = fmaf(al[r], fmaf(acc[r], inv, b[rt]), asv[r]);
+      uint2 hi, lo;
+      split4(make_float4(vv[0], vv[1], vv[2], vv[3]), hi, lo);
+      // frame t = 16 rt + cl: the hi plane at [t][0][col], lo at [t][1][col]
+      const int t = 16 * rt + cl;
+      const uint32_t off = t < T && colb < NCOL ? 2u * (uint32_t)(t * 2 * NCOL + colb) : OOB;
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hi), ro, off, 0, kAdjStAux);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lo), ro, off + 2u * NCOL, 0, kAdjStAux);
     }
   }
 #ifdef DSTD_STAMPS
@@ -2302,11 +2120,10 @@ constexpr bool tf_phase3() {
 // also runs a sample's 22 GC units in two rounds instead of three
 // (H36M; CMU / 3DPW, whose joints run in two chunks, spill at 168 VGPRs and
 // keep 8)
-#ifndef DSTD_TF_NW_H36M
-#define DSTD_TF_NW_H36M 12
-#endif
+// (8 at H36M: +2.2% forward)
+constexpr int kTfWavesH36M = 12;
 template <int T, int V>
-constexpr int tf_waves() { return T == 35 && V == 22 ? DSTD_TF_NW_H36M : 8; }
+constexpr int tf_waves() { return T == 35 && V == 22 ? kTfWavesH36M : 8; }
 
 // The body of k_temporal_fused for sample n on the workgroup's dynamic LDS
 // dsm (TFusedGeom::LDS bytes): the kernel below runs it once, k_block_fused
@@ -2411,9 +2228,8 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kg = lane >> 4, cl = lane & 15;
   if constexpr (C == 64) { TLH(3, 0) TLH(4, 0) }
-#ifdef DSTD_SETPRIO_TF  // (experiment, r05o: waves 4-11 +0.6%, 8-11 neutral at H36M -- off)
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= DSTD_SETPRIO_TF) __builtin_amdgcn_s_setprio(1);
-#endif
+  // (no static priority for the younger waves here, unlike k_spatial_hl:
+  // r05o, waves 4-11 +0.6%, 8-11 neutral at H36M)
 
   {
     for (int ch = 0; ch < Gm::NCHUNK; ++ch) {
@@ -2549,18 +2365,19 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
       // across tiles.  Cause, found in round 3: hipcc had scheduled a
       // 16x16x16 tail MFMA right behind a 16x16x32 one on the same
       // accumulator -- dstd_hilo.h, mixed-shape MFMA chains.  With the tail on its
-      // own accumulator, TPI 1/2 and HOISTW 0/1 are all bit-exact.)
-#ifndef DSTD_TF_TPI
-#define DSTD_TF_TPI 1
-#endif
-#ifndef DSTD_TF_HOISTW
-#define DSTD_TF_HOISTW 1  // (A/B r03a: -1..2% per launch at H36M / 3DPW, tie at CMU)
-#endif
-      constexpr int TPI = DSTD_TF_TPI;  // column tiles per iteration (independent chains)
-      // (u chunks: the W fragments re-read per tile -- hoisted, their 24
-      // registers are live through the whole chunk loop and phase 2 spills)
-      constexpr bool HW = DSTD_TF_HOISTW && !Gm::UCH;
-      // W_rm fragments of the chunk's row tiles (HOISTW: read once, held across tiles)
+      // own accumulator, TPI 1 / 2 and hoisted / re-read W fragments are all
+      // bit-exact.)
+      // column tiles per iteration (independent chains; 2 was exact and no
+      // faster).  Kept as a constant: written out for one tile, hipcc
+      // allocates registers differently and the kernel is no longer the
+      // measured one instruction for instruction
+      constexpr int TPI = 1;
+      // W fragments hoisted out of the tile loop (A/B r03a: -1..2% per launch
+      // at H36M / 3DPW, tie at CMU), except with u chunks: the W fragments
+      // re-read per tile -- hoisted, their 24 registers are live through the
+      // whole chunk loop and phase 2 spills
+      constexpr bool HW = !Gm::UCH;
+      // W_rm fragments of the chunk's row tiles (HW: read once, held across tiles)
       f16x8 wfh[HW ? RTC : 1][NS], wfo[HW ? RTC : 1][NS];
       f16x4 wth[HW ? RTC : 1], wto[HW ? RTC : 1];
       auto load_w = [&](int rt, f16x8 (&h)[NS], f16x8 (&o)[NS], f16x4& th4, f16x4& to4) {
@@ -2654,77 +2471,32 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
                                             fmaf(al[i].w, fmaf(acc[i][3], inv, b), as[i].w));
               uint2 hi, lo;
               split4(vv, hi, lo);
-#ifdef DSTD_TF_ST128  // (off: 0.7-1.1% slower forward, profiles/r05h_lds_layout_ab.txt)
-              // lanes kg and kg ^ 1 hold the 8 consecutive slots 8 (kg >> 1) ..
-              // + 7 of one joint: v_permlane16_swap trades the even row's lo
-              // quad for the odd row's hi quad, so the even lane stores the hi
-              // plane's 16 bytes and the odd lane the lo plane's -- one
-              // ds_write_b128 per lane (8-lane groups over 32 banks: the joint
-              // stride PJ puts 8 joints on 8 distinct bank quads) instead of two
-              // ds_write_b64 whose 16-lane groups can reach only 16 of the 32
-              // banks from 16-byte-aligned rows (2-way)
-              const auto sx = __builtin_amdgcn_permlane16_swap(hi.x, lo.x, false, false);
-              const auto sy = __builtin_amdgcn_permlane16_swap(hi.y, lo.y, false, false);
-              const bool odd = kg & 1;
-              const uint4 w4 = odd ? make_uint4(sx[0], sy[0], lo.x, lo.y) : make_uint4(hi.x, hi.y, sx[1], sy[1]);
-              if (jv < nv && colb[i] < NCOL) {
-                _Float16* dst = planes + jv * PJ + q[i] * SL + slot0[i] - (odd ? 4 : 0) + (odd ? UF * SL : 0);
-                *reinterpret_cast<uint4*>(dst) = w4;
-              }
-#else  // two 8-byte stores per lane (2-way bank conflicted, cheaper in VALU)
+              // two 8-byte stores per lane, 2-way bank conflicted (one
+              // conflict-free 16-byte store per lane after a
+              // v_permlane16_swap of the hi / lo quads costs more VALU: 0.7-1.1%
+              // slower forward, profiles/r05h_lds_layout_ab.txt)
               if (jv < nv && colb[i] < NCOL) {
                 _Float16* dst = planes + jv * PJ + q[i] * SL + slot0[i];
                 *reinterpret_cast<uint2*>(dst) = hi;
                 *reinterpret_cast<uint2*>(dst + UF * SL) = lo;
               }
-#endif
             }
           }
         }
       };
-#ifndef DSTD_TF_SKIP_P1  // (timing experiments: phase 2 alone)
       if (sep) tiles(std::true_type{});
       else tiles(std::false_type{});
-#endif
-#if defined(DSTD_TF_DEBUGW) && DSTD_TF_HOISTW
-      // (bisection build: the hoisted W registers after the tile loop against
-      // a fresh read of the same LDS words, workgroup 0, every lane)
-      if (blockIdx.x == 0 && ch == 0) {
-#pragma unroll
-        for (int rt = 0; rt < RTC; ++rt) {
-          f16x8 h2[NS], o2[NS];
-          f16x4 th2, to2;
-          load_w(rt, h2, o2, th2, to2);
-          const uint4 a0 = __builtin_bit_cast(uint4, wfh[rt][0]), a1 = __builtin_bit_cast(uint4, wfo[rt][0]);
-          const uint4 b0 = __builtin_bit_cast(uint4, h2[0]), b1 = __builtin_bit_cast(uint4, o2[0]);
-          const uint2 a2 = __builtin_bit_cast(uint2, wth[rt]), a3 = __builtin_bit_cast(uint2, wto[rt]);
-          const uint2 b2 = __builtin_bit_cast(uint2, th2), b3 = __builtin_bit_cast(uint2, to2);
-          unsigned* d = g_dbg_w + ((rt * NT + tid) * 24);
-          const unsigned v[24] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a3.x, a3.y,
-                                  b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b3.x, b3.y};
-          for (int i = 0; i < 24; ++i) d[i] = v[i];
-        }
-      }
-#endif
       if constexpr (C == 64) {
         if (ch == 0) { TLH(4, 2) }
       }
       // the phase-2 stage's loads now, its LDS writes after the barrier
-      // (-DDSTD_TF_STAGE_EARLY=0: both after it, as before round 6)
+      // (both after it, as before round 6: within +-0.2%)
       TemporalStageLoad<T, EPI, C, V, NT> stl;
-      if constexpr (DSTD_TF_STAGE_EARLY) stl.load(a, tid, Gm::NCHUNK > 1 ? opaque_zero() : 0);
+      stl.load(a, tid, Gm::NCHUNK > 1 ? opaque_zero() : 0);
       __syncthreads();  // planes complete; the phase-1 scratch is free
-      if constexpr (!DSTD_TF_STAGE_EARLY) stl.load(a, tid, Gm::NCHUNK > 1 ? opaque_zero() : 0);
       if constexpr (C == 64) {
         if (ch == 0) { TLH(3, 1) }
       }
-#ifdef DSTD_TF_DUMPP
-      // (bisection build: workgroup 0's planes of chunk 0 to g_dbg_planes)
-      if (blockIdx.x == 0 && ch == 0) {
-        const unsigned* src = reinterpret_cast<const unsigned*>(planes);
-        for (int i = tid; i < (int)(Gm::PLANES / 4) && i < 64 * 1024; i += NT) g_dbg_planes[i] = src[i];
-      }
-#endif
       // ---- phase 2: the stage, then the chunk's GC units ----
       stl.store(a, st, tid);
       __syncthreads();
@@ -2749,15 +2521,8 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
           bo[ut] = *reinterpret_cast<const uint4*>(base + (ok ? UF * SL + off : Gm::ZPAD));
         }
       };
-#ifndef DSTD_TF_P2PRIO  // (experiments: the younger waves' static priority in the joint units)
-#define DSTD_TF_P2PRIO 0
-#endif
-      if constexpr (DSTD_TF_P2PRIO) { if (wave >= 4) __builtin_amdgcn_s_setprio(1); }
-#ifndef DSTD_TF_SKIP_P2  // (timing experiments: phase 1 alone)
       temporal_units<T, EPI, C, V, true, decltype(load_adj), (NW <= 8 && !Gm::UCH), tf_res_acc(T, V), NUTC>(
           a, st, ub + wave, ub + nv, NW, load_adj, u0 / 16);
-#endif
-      if constexpr (DSTD_TF_P2PRIO) __builtin_amdgcn_s_setprio(0);
     }
   }
   // ---- phase 3: the next block's spatial adjacency planes of this sample
@@ -2765,19 +2530,9 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
   if constexpr (C == 64 && tf_phase3<T, V>()) {
     TLH(3, 2)
     if (fa.sn.out) {
-#ifndef DSTD_P3_PRELOAD  // (1: the static loads before the barrier -- r06q: 0.0% / -0.1% / +1.7%, off)
-#define DSTD_P3_PRELOAD 0
-#endif
-      SAdjStatic<T, V, NT> p3s;
-      if constexpr (DSTD_P3_PRELOAD) p3s.load(fa.sn, tid);
       __syncthreads();  // every unit's P/Q written (one CU: the workgroup-scope fences of the barrier suffice)
       TLH(2, 0)
-#ifndef DSTD_TF_P3PRIO  // (experiments: the same in phase 3)
-#define DSTD_TF_P3PRIO 0
-#endif
-      if constexpr (DSTD_TF_P3PRIO) { if (wave >= 4) __builtin_amdgcn_s_setprio(1); }
-      spatial_adj_sample<T, V, NT>(fa.sn, n, dsm, DSTD_P3_PRELOAD ? &p3s : nullptr);
-      if constexpr (DSTD_TF_P3PRIO) __builtin_amdgcn_s_setprio(0);
+      spatial_adj_sample<T, V, NT>(fa.sn, n, dsm);
     }
     TLH(3, 3)
   }
@@ -2812,6 +2567,7 @@ template <int T, int V, int CIN, int COUT, int EPI>
 __device__ __forceinline__ void block_fused_body(const SpatialHLArgs& sa, const TemporalFusedArgs& ta, const AdjHLArgs& s0,
                                                  const int n, unsigned char* dsm) {
   constexpr int NW = tf_waves<T, V>(), NT = 64 * NW;
+  static_assert(!TFusedGeom<T, V, EPI, COUT>::UCH, "pq_sink and tfused_pre write whole E / F rows (UF == T)");
   if constexpr (CIN == 64 && COUT == 64) { TLH(5, 0) }
   if constexpr (CIN == 6 && tf_phase3<T, V>()) {
     // conv_st_in: this block's own spatial planes from the model input (the
@@ -2849,12 +2605,10 @@ __device__ __forceinline__ void block_fused_body(const SpatialHLArgs& sa, const 
       }
     };
     // (three waves per SIMD: the identity residual loaded after the
-    // aggregations, as DSTD_HL_WPE=3 builds of k_spatial_hl do, or it spills)
-    // (h and the temporal P/Q: DSTD_BF_ST_AUX, the cache policy of their
-    // stores -- the same CU reads them back right after the barrier)
-#ifndef DSTD_BF_ST_AUX
-#define DSTD_BF_ST_AUX DSTD_GC_ST_AUX
-#endif
+    // aggregations, or it spills)
+    // (h and the temporal P/Q stores keep the write-through policy although
+    // the same CU reads them back right after the barrier: write-back
+    // measured 0.0% / -0.4% / -0.2%, not kept)
     // every unit also writes its frame's E / F rows of phase 1 (the tanh
     // GEMM's exp2 of its temporal P / Q -- the values it stores, the same
     // float operations as phase 1's prologue) straight into the phase-1
@@ -2873,21 +2627,13 @@ __device__ __forceinline__ void block_fused_body(const SpatialHLArgs& sa, const 
       Fl[TEF::row(t) + V + w] = __builtin_amdgcn_exp2f(eq1);
       return !(fabsf(ep0) <= 120.f && fabsf(ep1) <= 120.f && fabsf(eq0) <= 120.f && fabsf(eq1) <= 120.f);
     };
-    // (experiments: static VALU priority for the younger waves during the
-    // spatial units -- 1: waves 4-11 at 1, 2: 4-7 at 1 and 8-11 at 2, 3:
-    // 8-11 at 1; back to 0 for the temporal phases)
-#ifndef DSTD_BF_SETPRIO
-#define DSTD_BF_SETPRIO 1
-#endif
-    if constexpr (DSTD_BF_SETPRIO == 1) { if (wave >= 4) __builtin_amdgcn_s_setprio(1); }
-    if constexpr (DSTD_BF_SETPRIO == 2) {
-      if (wave >= 8) __builtin_amdgcn_s_setprio(2);
-      else if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-    }
-    if constexpr (DSTD_BF_SETPRIO == 3) { if (wave >= 8) __builtin_amdgcn_s_setprio(1); }
-    bad = spatial_units<V, CIN, COUT, decltype(load_adj_g), (NW > 8), DSTD_BF_ST_AUX, decltype(pq_sink)>(
+    // static VALU priority 1 for the younger waves (4-11) during the spatial
+    // units, back to 0 for the temporal phases (also tried: none, 4-7 at 1
+    // with 8-11 at 2, 8-11 alone: DESIGN.md section 4)
+    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
+    bad = spatial_units<V, CIN, COUT, decltype(load_adj_g), (NW > 8), decltype(pq_sink)>(
         a, st, n * T + wave, (n + 1) * T, NW, load_adj_g, pq_sink);
-    if constexpr (DSTD_BF_SETPRIO != 0) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
   }
   if constexpr (CIN == 64 && COUT == 64) { TLH(5, 1) }
   tfused_pre<T, V, EPI, COUT>(ta, dsm);
@@ -2990,14 +2736,11 @@ hipError_t adj_hl_run(const AdjHLArgs& a, hipStream_t s) {
     // column tiles over more workgroups -- each repeats the prologue, but the
     // launch is its prologue plus 1/nch of the tiles -- keeping at least half
     // the waves of a workgroup busy
-#ifndef DSTD_ADJ_CHUNK_PCT  // (experiments: workgroups aimed at, % of the CUs / the busy-wave floor's divisor)
-#define DSTD_ADJ_CHUNK_PCT 100
-#define DSTD_ADJ_CHUNK_DIV 2
-#endif
+    // (aiming at 0 / 50 / 75 / 200 / 400% of the CUs instead:
+    // profiles/r05ee_adj_chunk_ab.txt)
     const int sets = a.B * a.ngroups, cus = hl_num_cus();
     b.nchunk = Gm::NCHUNK;
-    if (sets * Gm::NCHUNK < cus)
-      b.nchunk = max(Gm::NCHUNK, min(cdiv(DSTD_ADJ_CHUNK_PCT * cus, 100 * sets), cdiv(Gm::NCT, cdiv(Gm::AW, DSTD_ADJ_CHUNK_DIV))));
+    if (sets * Gm::NCHUNK < cus) b.nchunk = max(Gm::NCHUNK, min(cdiv(cus, sets), cdiv(Gm::NCT, cdiv(Gm::AW, 2))));
   }
   const int grid = a.B * a.ngroups * b.nchunk;
   hipLaunchKernelGGL((k_adj_hl<MODE, NROW, K, NA>), dim3(grid), dim3(Gm::AT), 0, s, b);
@@ -3093,31 +2836,32 @@ hipError_t bfused_tv(const BlockFusedArgs& a, hipStream_t s) {
 }
 
 bool block_fused_supported(int T, int V, int cin, int cout, int epi) {
-#ifdef DSTD_NO_BFUSED
-  return false;
-#endif
   const bool shape = (T == 35 && (V == 22 || V == 25)) || (T == 40 && V == 23);
   return shape && ((cin == 64 && cout == 64 && epi == TEPI_ENC) || (cin == 6 && cout == 64 && epi == TEPI_IN) ||
                    (cin == 64 && cout == 3 && epi == TEPI_OUT));
 }
 
 bool block_fused_adj0_supported(int T, int V) {
-#ifdef DSTD_NO_BF_ADJ0
-  return false;
-#endif
   return block_fused_supported(T, V, 6, 64, TEPI_IN) && temporal_fused_phase3(T, V);
+}
+
+// phase 3's arguments (the next block's spatial adjacency, launch_adj_hl mode
+// 0's) fit the temporal GC g whose launch runs it: g writes the P/Q they read
+static bool phase3_args_ok(const TemporalHLArgs& g, const AdjHLArgs& sn) {
+  return temporal_fused_phase3(g.T, g.V) && g.C == 64 && g.pq && sn.pq == g.pq && sn.ngroups == 2 && !sn.xin &&
+         sn.pql.sch == 1 && !(sn.pql.st & 3) && !(sn.pql.sv & 3) && !(sn.pql.sn & 3) && !(sn.p_ch[0] & 3) &&
+         !(sn.p_ch[1] & 3) && sn.out;
 }
 
 hipError_t block_fused_args(const SpatialHLArgs& sa, const TemporalHLArgs& g, const AdjHLArgs& j, const AdjHLArgs* sn,
                             BlockFusedArgs* out, const AdjHLArgs* s0) {
+  // (p_ch[0] == 0 and a dense sample stride: pq_sink's E / F rows stand for
+  // the prologue's reads at pq + n * sn + p_ch[0])
   if (!block_fused_supported(g.T, g.V, sa.Cin, sa.Cout, g.epi) || sa.T != g.T || sa.V != g.V || sa.B != g.B ||
       sa.Cout != g.C || sa.y != g.h || sa.pq != j.pq || g.V != (int)(j.pql.st / 4) || j.pql.sch != 1 || j.pql.sv != 4 ||
-      ((uintptr_t)j.pq & 15))
+      ((uintptr_t)j.pq & 15) || j.p_ch[0] != 0 || j.pql.sn != (long)g.T * g.V * 4)
     return hipErrorNotSupported;
-  if (sn && (!temporal_fused_phase3(g.T, g.V) || g.C != 64 || !g.pq || sn->pq != g.pq || sn->ngroups != 2 || sn->xin ||
-             sn->pql.sch != 1 || (sn->pql.st & 3) || (sn->pql.sv & 3) || (sn->pql.sn & 3) || (sn->p_ch[0] & 3) ||
-             (sn->p_ch[1] & 3) || !sn->out))
-    return hipErrorNotSupported;
+  if (sn && !phase3_args_ok(g, *sn)) return hipErrorNotSupported;
   if (s0 && (sa.Cin != 6 || !block_fused_adj0_supported(g.T, g.V) || !s0->xin || s0->ngroups != 2 || !s0->out ||
              s0->B != g.B || !sa.xmodel || sa.adj != s0->out))
     return hipErrorNotSupported;
@@ -3143,11 +2887,7 @@ bool temporal_fused_supported(int T, int V) {
 // asked (DSTD_FWD_FUSED_TEMPORAL) -- measured 8.8% slower per forward than the
 // unfused pair (profiles/r05h_t75_fused_ab.txt)
 bool temporal_fused_default(int T, int V) {
-#ifdef DSTD_TF75_DEFAULT
-  return temporal_fused_supported(T, V);
-#else
   return temporal_fused_supported(T, V) && T != 75;
-#endif
 }
 bool temporal_fused_phase3(int T, int V) {
   if (T == 35 && V == 22) return tf_phase3<35, 22>();
@@ -3161,10 +2901,7 @@ hipError_t launch_temporal_fused(const TemporalHLArgs& g, const AdjHLArgs& j, co
   if (!temporal_fused_supported(g.T, g.V) || g.V != (int)(j.pql.st / 4) || j.pql.sch != 1 || j.pql.sv != 4 ||
       ((uintptr_t)j.pq & 15))
     return hipErrorNotSupported;
-  if (sn && (!temporal_fused_phase3(g.T, g.V) || g.C != 64 || !g.pq || sn->pq != g.pq || sn->ngroups != 2 || sn->xin || sn->pql.sch != 1 ||
-             (sn->pql.st & 3) || (sn->pql.sv & 3) || (sn->pql.sn & 3) || (sn->p_ch[0] & 3) || (sn->p_ch[1] & 3) ||
-             !sn->out))
-    return hipErrorNotSupported;
+  if (sn && !phase3_args_ok(g, *sn)) return hipErrorNotSupported;
   const TemporalFusedArgs a{g, j, sn ? *sn : AdjHLArgs{}};
   if (g.T == 35 && g.V == 22) return tfused_tv<35, 22>(a, s);
   if (g.T == 35 && g.V == 25) return tfused_tv<35, 25>(a, s);

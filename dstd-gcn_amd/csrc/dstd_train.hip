@@ -322,9 +322,6 @@ __device__ __forceinline__ float cs_ld(__amdgpu_buffer_rsrc_t r, uint32_t off) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
 }
 __device__ __forceinline__ void cs_st(__amdgpu_buffer_rsrc_t r, uint32_t off, float v) {
-#if defined(DSTD_CS_ABL) && (DSTD_CS_ABL & 2)  // (ablation builds: stores dropped)
-  if (v != 12345.f) off = kCsOOB;
-#endif
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, off, 0, 0);
 }
 // Launch constants of k_conv_stream (byte strides of one batch's panels)
@@ -332,15 +329,12 @@ struct CsArgs {
   int ntile, nb2;
   uint32_t b_bytes, c_bytes;  // one batch's B / C extent (buffer ranges)
 };
-#ifndef DSTD_CS_NT  // 16-column tiles per item (experiments: 1, 2, 4)
-#define DSTD_CS_NT 1
-#endif
-#ifndef DSTD_CS_PF  // next item's B fragments loaded during this item's MFMAs
-#define DSTD_CS_PF 1
-#endif
 template <int MF, int KS>
 __global__ __launch_bounds__(256) void k_conv_stream(Gemm g, CsArgs ca) {
-  constexpr int NT = DSTD_CS_NT, PF = DSTD_CS_PF;
+  // 16-column tiles per item (2 and 4 measured: profiles/r04v_train_ab.txt;
+  // gemm_stream's ntile assumes 1).  Kept as a constant: written out for one
+  // tile, hipcc allocates registers differently
+  constexpr int NT = 1;
   // A in LDS in fragment order, four k-steps per lane per 16-byte read:
   // As[((x KS4 + s4) 64 + lane) 4 + j] = A[16x + lr][4 (4 s4 + j) + lk]
   constexpr int KS4 = (KS + 3) / 4;
@@ -393,15 +387,12 @@ __global__ __launch_bounds__(256) void k_conv_stream(Gemm g, CsArgs ca) {
   };
   int it = blockIdx.x * 4 + wave;
   float bf[NT][KS];
-  if (PF && it < items) load(it, bf);
+  if (it < items) load(it, bf);
   for (; it < items; it += nw) {
+    // the next item's B fragments, loaded during this item's MFMAs
     float bn[NT][KS];
-    if constexpr (PF) {
-      const int nx = it + nw;
-      load(nx < items ? nx : it, bn);  // the next item's fragments (the last reloads its own)
-    } else {
-      load(it, bf);
-    }
+    const int nx = it + nw;
+    load(nx < items ? nx : it, bn);  // (the last item reloads its own)
     const float* Bb;
     float* Cb;
     float* Db;
@@ -429,11 +420,6 @@ __global__ __launch_bounds__(256) void k_conv_stream(Gemm g, CsArgs ca) {
 #pragma unroll
       for (int x = 0; x < MF; ++x) acc[q][x] = zero4();
     const int lz = lane + cs_opaque_zero();
-#if defined(DSTD_CS_ABL) && (DSTD_CS_ABL & 1)  // (ablation builds: no MFMAs)
-#pragma unroll
-    for (int sk = 0; sk < KS; ++sk) acc[0][sk % MF][sk & 3] += bf[0][sk];
-    if (lz < 0)
-#endif
 #pragma unroll
     for (int s4 = 0; s4 < KS4; ++s4) {
       float4 a[MF];
@@ -487,12 +473,10 @@ __global__ __launch_bounds__(256) void k_conv_stream(Gemm g, CsArgs ca) {
           }
       }
     }
-    if constexpr (PF) {
 #pragma unroll
-      for (int q = 0; q < NT; ++q)
+    for (int q = 0; q < NT; ++q)
 #pragma unroll
-        for (int sk = 0; sk < KS; ++sk) bf[q][sk] = bn[q][sk];
-    }
+      for (int sk = 0; sk < KS; ++sk) bf[q][sk] = bn[q][sk];
   }
 }
 
@@ -1043,11 +1027,9 @@ __global__ __launch_bounds__(kAggcThreads) void k_aggc(AggArgs g) {
 // place of the a's dy slots.  The cdiv(C, CW) partials are summed in a fixed
 // order by adj_bwd (deterministic).  CW = 16 MF channels: 16 (temporal), 64
 // (spatial, MF = 4 row tiles of dF per a).
-#ifndef DSTD_AGGCB_THREADS  // (experiments: waves per workgroup x 64)
-#define DSTD_AGGCB_THREADS 512  // (spatial: 8 waves, B=32 step -1.3%, profiles/r05z_aggcb_waves_ab.txt)
-#endif
-// (the temporal instantiations keep 4 waves: at 8, JF = 3 spills)
-__host__ __device__ constexpr int aggcb_threads(bool temporal) { return temporal ? 256 : DSTD_AGGCB_THREADS; }
+// (spatial: 8 waves, B=32 step -1.3%, profiles/r05z_aggcb_waves_ab.txt; the
+// temporal instantiations keep 4 waves: at 8, JF = 3 spills)
+__host__ __device__ constexpr int aggcb_threads(bool temporal) { return temporal ? 256 : 512; }
 template <bool TEMP, int JF, int MF>
 __global__ __launch_bounds__(aggcb_threads(TEMP)) void k_aggc_bwd(AggArgs g) {
   constexpr int kAggcbThreads = aggcb_threads(TEMP);
@@ -1287,9 +1269,9 @@ __global__ void k_tanh_outer_bwd(const float* __restrict__ M, const float* __res
 // Fused adjacency backward, stage 1: workgroup (row a, sample chunk); each
 // thread owns entries ij and walks the chunk's samples (no atomics).
 // stage 1: workgroup (a, sample chunk, column block): the chunk's samples 8
-// at a time with every load in flight.  DSTD_ADJ_SPLIT (default): 256-column
-// blocks, one (i, j) per thread; 0: one block per (a, chunk), a 3-trip
-// column loop (profiles/r04u_train_switches_ab.txt)
+// at a time with every load in flight.  256-column blocks, one (i, j) per
+// thread (against one block per (a, chunk) with a 3-trip column loop: B=256
+// step 27.9 -> 27.0 ms, B=32 neutral, profiles/r04u_train_switches_ab.txt)
 __global__ __launch_bounds__(256) void k_adj_bwd_part(float* __restrict__ dD, const float* __restrict__ E,
                                                       const float* __restrict__ alpha, int B, int A, int NN2, int nch,
                                                       float* __restrict__ pdA, float* __restrict__ pbr,
@@ -1600,10 +1582,7 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 // Rows are visited RB at a time with all RB loads issued before the first
 // use (a row-at-a-time loop pays one memory latency per row, ~8 per chunk at
 // the config-5 batch); the accumulation order is unchanged.
-#ifndef DSTD_BN_RB  // (experiments)
-#define DSTD_BN_RB 8
-#endif
-constexpr int kBnRB = DSTD_BN_RB;
+constexpr int kBnRB = 8;
 struct BnRows {  // the rows row0, row0 + S, ... of one batch as (n, t)
   int n[kBnRB], t[kBnRB];
   bool ok[kBnRB];
@@ -1889,10 +1868,7 @@ __global__ __launch_bounds__(256) void k_bn_apply_merged(BnFwd a, int B, int C, 
     }
     return;
   }
-#ifndef DSTD_BN_APPLY_EB
-#define DSTD_BN_APPLY_EB 4
-#endif
-  constexpr int EB = DSTD_BN_APPLY_EB;  // elements per thread per batch, loads issued first
+  constexpr int EB = 4;  // elements per thread per batch, loads issued first
   for (int k = 0; k < ns; ++k)
   for (int e0 = tid; e0 < T * V; e0 += EB * 256) {
     const size_t base = ((size_t)(n + k) * C + c) * T * V;
@@ -1988,7 +1964,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_local_sums(int cv, int groups, i
   dst[((size_t)g * cv + ch) * 2 + 1] = sdx;
 }
 
-// DSTD_BN_SEP backward: the merge as a launch of its own (one thread per
+// bn_sep() backward: the merge as a launch of its own (one thread per
 // channel: the group sums in split order into sx[group][C*V][2] -- SyncBN's
 // all-reduced ones for the input gradient -- dgamma / dbeta, and workgroup 0
 // the PReLU slope), then a flat float4 apply.  Same arithmetic as
@@ -2347,9 +2323,6 @@ void sk_go(K kern, int grid, size_t lds, hipStream_t s, Args... args) {
   }
   kern<<<grid, 256, lds, s>>>(args...);
 }
-#ifndef DSTD_GEMM_STREAM  // (r04u: B=256 step 27.9 -> 25.2 ms, B=32 -0.5%; 0 = the panel / tile kernels)
-#define DSTD_GEMM_STREAM 1
-#endif
 template <int MF, int KS>
 hipError_t cs_go(const Gemm& g, int ntile, hipStream_t s) {
   static const int occ = [] {
@@ -2372,11 +2345,7 @@ hipError_t cs_go(const Gemm& g, int ntile, hipStream_t s) {
   // workgroups, leaving CUs to the weight-gradient stream's reductions that
   // run beside it (B=32 step -1.3%); a large one the whole chip (half of it
   // measured +2% at B=256; profiles/r04w_train_ab.txt)
-#ifndef DSTD_CS_GRID_DIV  // (experiments: a fixed divisor)
   const int div = items < 16384 ? 2 : 1;
-#else
-  const int div = DSTD_CS_GRID_DIV;
-#endif
   const int grid = (int)std::max(1L, std::min((long)cus * occ / div, (items + 3) / 4));
   CsArgs ca;
   ca.ntile = ntile;
@@ -2398,24 +2367,22 @@ hipError_t cs_ks(const Gemm& g, int ntile, hipStream_t s) {
   if (ks <= 17) return cs_go<MF, 17>(g, ntile, s);
   return cs_go<MF, 20>(g, ntile, s);
 }
-// hipErrorNotSupported: not a streaming shape (nothing launched)
+// hipErrorNotSupported: not a streaming shape (nothing launched): those go to
+// the panel / tile kernels (as every shape did before r04u: B=256 step 27.9 ->
+// 25.2 ms, B=32 -0.5%)
 hipError_t gemm_stream(const Gemm& g, hipStream_t s) {
   // (one A shared by every batch: it is staged once per workgroup)
-  if (!DSTD_GEMM_STREAM || g.reduce || g.a_b1 || g.a_b2 || g.b_n != 1 || g.c_n != 1 || g.b_ones_last || g.nseg || g.M > kCsMax ||
+  if (g.reduce || g.a_b1 || g.a_b2 || g.b_n != 1 || g.c_n != 1 || g.b_ones_last || g.nseg || g.M > kCsMax ||
       g.K > kCsMax || g.K < 1 || g.N < 16)
     return hipErrorNotSupported;
   const long long nbat = (long long)g.nb1 * g.nb2;
-  const int ntile = cdiv(g.N, 16 * DSTD_CS_NT);  // items per batch
+  const int ntile = cdiv(g.N, 16);  // items per batch
   // 32-bit buffer offsets over one batch's panels
   // (rows past K / M are read / written at offsets past the buffer range: the
   // padded k-steps and row tiles must stay below 2^31 bytes too)
   if (nbat * ntile >= (1LL << 31) || g.b_k < g.N || g.c_m < g.N || ((long long)g.K + 84) * g.b_k * 4 >= (1LL << 31) ||
       ((long long)g.M + 16) * g.c_m * 4 >= (1LL << 31))
     return hipErrorNotSupported;
-#ifdef DSTD_GEMM_LOG
-  fprintf(stderr, "gemm stream M %d N %d K %d nb %lld beta %g bias %d d_out %d stream %p\n", g.M, g.N, g.K, nbat, g.beta,
-          g.bias_m != nullptr, g.d_out != nullptr, (void*)s);
-#endif
   switch (cdiv(g.M, 16)) {
     case 1: return cs_ks<1>(g, ntile, s);
     case 2: return cs_ks<2>(g, ntile, s);
@@ -2436,10 +2403,6 @@ hipError_t gemm_skinny(const Gemm& g, float* scratch, hipStream_t s) {
     const int MF = cdiv(g.M, 16), K4 = rup(g.K, 4), KP = sk_pitch(K4, 4), BP = sk_pitch(kSkPT, 16);
     const size_t lds = sizeof(float) * ((size_t)MF * 16 * KP + (size_t)K4 * BP);
     const int grid = nbat * cdiv(g.N, kSkPT);
-#ifdef DSTD_GEMM_LOG
-    fprintf(stderr, "gemm skinny MF %d M %d N %d K %d nb %d beta %g bias %d stream %p\n", MF, g.M, g.N, g.K, nbat, g.beta,
-            g.bias_m != nullptr, (void*)s);
-#endif
     const int vec = g.N % 4 == 0 && g.b_k % 4 == 0 && g.b_b1 % 4 == 0 && g.b_b2 % 4 == 0 &&
                     ((uintptr_t)g.B & 15) == 0;
     switch (MF) {
@@ -2489,11 +2452,6 @@ hipError_t gemm(const Gemm& g, float* scratch, hipStream_t s, GemmFinish* defer)
   }
   dim3 grid(cdiv(g.N, TN), cdiv(g.M, TM), g.reduce ? nsplit : nbat);
   float* part = nsplit > 1 ? scratch : nullptr;
-#ifdef DSTD_GEMM_LOG  // (debug builds: the shape mix of a training step)
-  fprintf(stderr, "gemm tile %dx%d M %d N %d K %d nb %d reduce %d nsplit %d a_m %lld a_k %lld b_k %lld b_n %lld c_m %lld "
-          "c_n %lld d_out %d nseg %d bias %d beta %g stream %p\n", TM, TN, g.M, g.N, g.K, nbat, g.reduce, nsplit, g.a_m,
-          g.a_k, g.b_k, g.b_n, g.c_m, g.c_n, g.d_out != nullptr, g.nseg, g.bias_m != nullptr, g.beta, (void*)s);
-#endif
 #define DSTD_GEMM_GO(tm, tn) \
   if (TM == tm && TN == tn) k_gemm<tm, tn><<<grid, 256, 0, s>>>(g, nsplit, kch, kc_len, part)
   DSTD_GEMM_GO(32, 32); else DSTD_GEMM_GO(32, 64); else DSTD_GEMM_GO(64, 32); else DSTD_GEMM_GO(64, 64);
@@ -2548,27 +2506,22 @@ int agg_cus() {
   }();
   return n;
 }
-// Channel-chunk kernels, spatial: below DSTD_AGG_SPLIT_WG (sample, chunk)
+// Channel-chunk kernels, spatial: below kAggSplitWgPerCu (sample, chunk)
 // workgroups per CU, the frames of each are split over several workgroups of
 // apg frames (apg * V a multiple of 4: 16-byte runs stay aligned), so the
 // config-5 batch (64 samples x 4 chunks: one workgroup and 4 waves per CU)
-// gets ~per_cu workgroups per CU (2 each way: B=32 step 4.725 -> 4.671 ms;
+// gets about that many workgroups per CU (2 each way, k_aggc and k_aggc_bwd: B=32 step 4.725 -> 4.671 ms;
 // forward alone 4.698, backward alone 4.683, a forward target of 4: 4.739;
 // profiles/r05q_agg_split_ab.txt); sets g.asplit / g.apg and returns the
 // widest slab (floats per channel row)
-#ifndef DSTD_AGG_SPLIT_WG  // forward (k_aggc); experiments: 0 = no split
-#define DSTD_AGG_SPLIT_WG 2
-#endif
-#ifndef DSTD_AGGB_SPLIT_WG  // backward (k_aggc_bwd)
-#define DSTD_AGGB_SPLIT_WG 2
-#endif
-int agg_split(AggArgs& g, int B, bool temporal, int per_cu, int cw = 16) {
+constexpr int kAggSplitWgPerCu = 2;
+int agg_split(AggArgs& g, int B, bool temporal, int cw) {
   g.asplit = 1;
   g.apg = g.A;
   const int wgs = B * cdiv(g.C, cw), cus = agg_cus();
-  if (temporal || per_cu <= 0 || wgs >= per_cu * cus) return g.TV;
+  if (temporal || wgs >= kAggSplitWgPerCu * cus) return g.TV;
   const int m = (g.V % 4 == 0) ? 1 : (g.V % 2 == 0) ? 2 : 4;
-  const int want = std::min(g.A, cdiv(per_cu * cus, wgs));
+  const int want = std::min(g.A, cdiv(kAggSplitWgPerCu * cus, wgs));
   g.apg = std::min(g.A, rup(cdiv(g.A, want), m));
   g.asplit = cdiv(g.A, g.apg);
   return g.apg * g.V;
@@ -2609,16 +2562,12 @@ hipError_t agg_launch_a(bool bwd, bool df, AggArgs g, int B, int temporal, hipSt
 // channel-chunk kernel: fwd (trans 0) or dF (trans 1)
 hipError_t agg_launch_c(bool trans, AggArgs g, int B, int temporal, hipStream_t s) {
   if (!agg_ok(g)) return hipErrorNotSupported;
-  // channels per chunk: 16; the spatial forward DSTD_AGG_CW_SP (16 or 64: a
-  // wider chunk reads D once per chunk, but 64 measured +0.7% at B=32, +1.7%
-  // at B=256 -- half its waves idle over 4 frames; profiles/r05jj_agg_cw_ab.txt)
-#ifndef DSTD_AGG_CW_SP
-#define DSTD_AGG_CW_SP 16
-#endif
-  // (row tiles 1 or 4: 2 and 3 run as 4, cv masking the rest)
-  const int mfc = temporal || trans || DSTD_AGG_CW_SP < 64 || g.C <= 16 ? 1 : 4, cw = 16 * mfc;
+  // channels per chunk: 16, one row tile (on the spatial forward a 64-channel
+  // chunk reads D once per chunk, but measured +0.7% at B=32, +1.7% at B=256
+  // -- half its waves idle over 4 frames; profiles/r05jj_agg_cw_ab.txt)
+  constexpr int cw = 16;
   agg_tile(g.NN, g.RK, g.P);
-  g.QP = agg_split(g, B, temporal, DSTD_AGG_SPLIT_WG, cw);
+  g.QP = agg_split(g, B, temporal, cw);
   while ((g.QP & 63) != 4) ++g.QP;
   const size_t lds = sizeof(float) * ((size_t)cw * g.QP + (size_t)(kAggcThreads / 64) * g.RK * g.P);
   if (lds > 160 * 1024) return hipErrorNotSupported;
@@ -2626,25 +2575,19 @@ hipError_t agg_launch_c(bool trans, AggArgs g, int B, int temporal, hipStream_t 
            ((uintptr_t)g.O & 15) == 0);
   const dim3 grid(B * cdiv(g.C, cw) * g.asplit), block(kAggcThreads);
   const int jf = cdiv(g.NN, 16);
-  auto pick = [&](auto tb, auto rb, auto mb) {
+  auto pick = [&](auto tb, auto rb) {
     constexpr bool T_ = decltype(tb)::value, R_ = decltype(rb)::value;
-    constexpr int M_ = decltype(mb)::value;
     switch (jf) {
-      case 1: agg_go(k_aggc<T_, R_, 1, M_>, grid, block, lds, g, s); break;
-      case 2: agg_go(k_aggc<T_, R_, 2, M_>, grid, block, lds, g, s); break;
-      case 3: agg_go(k_aggc<T_, R_, 3, M_>, grid, block, lds, g, s); break;
-      default: agg_go(k_aggc<T_, R_, 4, M_>, grid, block, lds, g, s); break;
+      case 1: agg_go(k_aggc<T_, R_, 1, 1>, grid, block, lds, g, s); break;
+      case 2: agg_go(k_aggc<T_, R_, 2, 1>, grid, block, lds, g, s); break;
+      case 3: agg_go(k_aggc<T_, R_, 3, 1>, grid, block, lds, g, s); break;
+      default: agg_go(k_aggc<T_, R_, 4, 1>, grid, block, lds, g, s); break;
     }
   };
   using T1 = std::true_type;
   using F0 = std::false_type;
-  using M1 = std::integral_constant<int, 1>;
-  if (temporal) trans ? pick(T1(), T1(), M1()) : pick(T1(), F0(), M1());
-  else if (trans) pick(F0(), T1(), M1());
-  else if (mfc == 1) pick(F0(), F0(), M1());
-#if DSTD_AGG_CW_SP >= 64
-  else pick(F0(), F0(), std::integral_constant<int, 4>());
-#endif
+  if (temporal) trans ? pick(T1(), T1()) : pick(T1(), F0());
+  else trans ? pick(F0(), T1()) : pick(F0(), F0());
   return hipGetLastError();
 }
 AggArgs agg_geom(int C, int T, int V, int temporal) {
@@ -2679,18 +2622,15 @@ hipError_t agg_bwd(const float* F, long long fs, const float* dy, long long dys,
   // dF on the channel-chunk backward kernel, dD as its per-chunk partials
   // (dDpart; one chunk: dD itself); else dF on the channel-chunk kernel and
   // dD on the a-chunk kernel
-  // channels per chunk: 16 (temporal); spatial DSTD_AGGB_CW_SP: one chunk
+  // channels per chunk: 16 (temporal); spatial up to 64: one chunk
   // of all 64 channels reads D once and leaves one dD (no partials for
   // adj_bwd_part to sum): B=32 step -1.3%, profiles/r05gg_aggb_cw_ab.txt
-#ifndef DSTD_AGGB_CW_SP
-#define DSTD_AGGB_CW_SP 64
-#endif
   // (row tiles 1, 2 or 4: 3 runs as 4, cv masking the fourth).  When the
   // preferred chunk's slab does not fit LDS (large batches split fewer frames
   // per workgroup: H36M / 3DPW at B=256 need 231-264 KB at 64 channels) the
   // 16-channel chunk is tried before the two-launch path (dF kernel + dD
   // a-chunk kernel)
-  const int mf_pref = temporal ? 1 : std::min(DSTD_AGGB_CW_SP / 16, cdiv(C, 16));
+  const int mf_pref = temporal ? 1 : std::min(4, cdiv(C, 16));
   const int tries[2] = {mf_pref == 3 ? 4 : mf_pref, 1};
   for (int ti = 0; ti < (tries[0] == 1 ? 1 : 2); ++ti) {
     const int mfc = tries[ti], cw = 16 * mfc;
@@ -2699,7 +2639,7 @@ hipError_t agg_bwd(const float* F, long long fs, const float* dy, long long dys,
     g.dD = cch > 1 ? dDpart : dD;
     g.B = B;
     agg_tile(g.NN, g.RK, g.P);
-    g.QP = agg_split(g, B, temporal, DSTD_AGGB_SPLIT_WG, cw);
+    g.QP = agg_split(g, B, temporal, cw);
     while ((g.QP & 63) != 4) ++g.QP;
     const int nth = aggcb_threads(temporal);
     const size_t lds = sizeof(float) * ((size_t)2 * cw * g.QP + (size_t)(nth / 64) * g.RK * g.P);
@@ -2722,12 +2662,8 @@ hipError_t agg_bwd(const float* F, long long fs, const float* dy, long long dys,
     };
     if (temporal) pick(std::true_type(), std::integral_constant<int, 1>());
     else if (mfc == 1) pick(std::false_type(), std::integral_constant<int, 1>());
-#if DSTD_AGGB_CW_SP >= 32
     else if (mfc == 2) pick(std::false_type(), std::integral_constant<int, 2>());
-#endif
-#if DSTD_AGGB_CW_SP >= 64
     else pick(std::false_type(), std::integral_constant<int, 4>());
-#endif
     return hipGetLastError();
   }
   *nparts = 1;
@@ -2779,9 +2715,6 @@ size_t adj_bwd_scratch_floats(int B, int A, int NN2) {
   return (size_t)nch * A * NN2 + 3 * (size_t)nch * A * cdiv(NN2, 256) + 64;  // pal: doubles
 }
 
-#ifndef DSTD_ADJ_SPLIT  // (r04u: B=256 step 27.9 -> 27.0 ms, B=32 neutral; 0 = one column block)
-#define DSTD_ADJ_SPLIT 1
-#endif
 namespace {
 // the partials' layout in scratch (256-byte aligned workspace carve): pal
 // (doubles), then pdA, then pbr
@@ -2790,7 +2723,7 @@ struct AdjBwdScratch {
   double* pal;
   float *pdA, *pbr;
   AdjBwdScratch(float* scratch, int B, int A, int NN2)
-      : nch(adj_bwd_chunks(B, A)), nij(DSTD_ADJ_SPLIT ? cdiv(NN2, 256) : 1) {
+      : nch(adj_bwd_chunks(B, A)), nij(cdiv(NN2, 256)) {
     pal = reinterpret_cast<double*>(scratch);
     pdA = scratch + 2 * (size_t)nch * A * nij;
     pbr = pdA + (size_t)nch * A * NN2;
@@ -2911,24 +2844,8 @@ hipError_t acc_mul(const float* a, const float* b, float* out, size_t n, hipStre
 // Separate merge + flat apply for large batches only: at the config-5 batch
 // (3.8M elements per BN) the 30 merge launches cost more than the re-merges
 // they save (+4%), at B=256 they save 2% (profiles/r04y_bn_sep_ab.txt).
-// DSTD_BN_SEP=0 / 1 forces it.
-bool bn_sep(long long total) {
-#ifdef DSTD_BN_SEP
-  (void)total;
-  return DSTD_BN_SEP;
-#else
-  return total >= (1LL << 24);
-#endif
-}
-#ifndef DSTD_BN_NOVEC  // (A/B builds: the scalar element loops)
-constexpr bool kBnVec = true;
-#else
-constexpr bool kBnVec = false;
-#endif
+bool bn_sep(long long total) { return total >= (1LL << 24); }
 int bn_apply_samples(int Bg, int B, int C) {
-#ifdef DSTD_BN_NS  // (experiments: samples per apply workgroup)
-  if (Bg % DSTD_BN_NS == 0) return DSTD_BN_NS;
-#endif
   // (>= 1024 workgroups: 4 samples each at the config-5 batch, a quarter of
   // the per-workgroup merges; B=32 step -1.4%, profiles/r04ad_bn_ns_ab.txt)
   for (int ns : {4, 2})
@@ -2938,7 +2855,7 @@ int bn_apply_samples(int Bg, int B, int C) {
 
 int bn_splits(int B, int T) { return std::max(1, std::min(kBnMaxSplits, cdiv(B * T, 64))); }
 
-size_t bn_scratch_floats(int B, int C, int T, int V) {  // sized for up to 2 groups (+ DSTD_BN_SEP's scale / shift)
+size_t bn_scratch_floats(int B, int C, int T, int V) {  // sized for up to 2 groups (+ bn_sep()'s scale / shift)
   return 2 * ((size_t)bn_splits(B, T) * C * V * 2 + (size_t)bn_splits(B, T) * C) + (size_t)2 * C * V + (size_t)4 * C * V;
 }
 
@@ -2975,7 +2892,7 @@ hipError_t bn_train_fwd(const BnFwd& a, int B, int C, int T, int V, float* scrat
     return hipGetLastError();
   }
   const int ns = bn_apply_samples(B / a.groups, B, C);
-  if (kBnVec && (T * V) % 4 == 0 && al && ns <= 4)
+  if ((T * V) % 4 == 0 && al && ns <= 4)
     k_bn_apply_merged<true><<<dim3(C, B / ns), 256, 0, s>>>(b, B, C, T, V, splits, scratch, ns);
   else
     k_bn_apply_merged<false><<<dim3(C, B / ns), 256, 0, s>>>(b, B, C, T, V, splits, scratch, ns);
@@ -3017,7 +2934,7 @@ hipError_t bn_train_bwd(const BnBwd& a, int B, int C, int T, int V, float* scrat
     }
   }
   const int ns = bn_apply_samples(B / a.groups, B, C);
-  if (kBnVec && (T * V) % 4 == 0 && al && ns <= 4)
+  if ((T * V) % 4 == 0 && al && ns <= 4)
     k_bn_bwd_apply_merged<true><<<dim3(C, B / ns), 256, 0, s>>>(b, B, C, T, V, splits, part, wpart, dprelu, ns);
   else
     k_bn_bwd_apply_merged<false><<<dim3(C, B / ns), 256, 0, s>>>(b, B, C, T, V, splits, part, wpart, dprelu, ns);

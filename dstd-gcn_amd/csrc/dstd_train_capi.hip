@@ -174,9 +174,6 @@ struct WgradRes {
 // get different sets, consecutive calls share one.
 std::mutex g_wgrad_mu;
 WgradRes* wgrad_acquire() {
-#ifdef DSTD_TRAIN_NO_WGRAD_STREAM
-  return nullptr;
-#else
   static std::vector<WgradRes*> pool;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return nullptr;
@@ -201,7 +198,6 @@ WgradRes* wgrad_acquire() {
   r->busy = true;
   pool.push_back(r);
   return r;
-#endif
 }
 void wgrad_release(WgradRes* r) {
   if (!r) return;
@@ -428,24 +424,17 @@ hipError_t op_bwd(const OpGeom& g, const float* x, const dstd_gc_weights* w, con
   // dalpha, dA, d b_rm from the partials -- parameter gradients only, so on
   // the weight-gradient stream when there is one (B=32 step: 21 finishes off
   // the critical path), with the partials in the op's set
-#ifndef DSTD_ADJ_FINISH_MAIN  // (A/B: 1 = the finish on the caller's stream, before the fork)
-#define DSTD_ADJ_FINISH_MAIN 0
-#endif
   // With the weight-gradient stream, this finish and the two reductions'
   // split-K finishes below run as ONE launch after dWp's reduction
-  // (finish_set: 2 launches per op fewer; dW_rm's partials in gs3)
+  // (finish_set: 2 launches per op fewer; dW_rm's partials in gs3; the
+  // finish on the caller's stream before the fork, or the three finishes as
+  // launches of their own on the side stream, were A/B-ed: DESIGN.md section 4)
   float* const adjs = wg->res ? ws0.adjp[slot] : ws.red;
   DSTD_TRYH(adj_bwd_part(ws.dD, sv.E, alpha, g.B, g.A, g.NN2, adjs, s, ws.dDp, nparts));
-  if (DSTD_ADJ_FINISH_MAIN || !wg->res)
-    DSTD_TRYH(adj_bwd_finish(g.B, g.A, g.NN2, dA, gr->brm, dalpha, adjs, s, assign_dA, dW2, Amul));
+  const bool fset = wg->res != nullptr;
+  if (!fset) DSTD_TRYH(adj_bwd_finish(g.B, g.A, g.NN2, dA, gr->brm, dalpha, adjs, s, assign_dA, dW2, Amul));
   if (wg->res) DSTD_TRYH(wg->fork());
-#ifndef DSTD_FINISH_SET  // (A/B: 0 = the three finishes as launches of their own on the side stream)
-#define DSTD_FINISH_SET 1
-#endif
   GemmFinish wrf, gwf;
-  const bool fset = wg->res && !DSTD_ADJ_FINISH_MAIN && DSTD_FINISH_SET;
-  if (wg->res && !DSTD_ADJ_FINISH_MAIN && !fset)
-    DSTD_TRYH(adj_bwd_finish(g.B, g.A, g.NN2, dA, gr->brm, dalpha, adjs, ws_s, assign_dA, dW2, Amul));
   const float* dE = ws.dD;
   Gemm wr;  // dWrm[a][k] = sum_{n,ij} dE[n][a][ij] M[n][k][ij]
   wr.M = g.A, wr.N = g.R * g.A, wr.K = g.NN2, wr.nb1 = g.B, wr.reduce = 1;
@@ -474,9 +463,8 @@ hipError_t op_bwd(const OpGeom& g, const float* x, const dstd_gc_weights* w, con
   gw.seg[2] = Gemm::Seg{g.cout + g.R, g.R, gr->wm2, gr->bm2};
   if (wg->res) {  // queued before dx, which then runs beside it
     DSTD_TRYH(wg->fork());
-    DSTD_TRYH(gemm(gw, ws_gs, ws_s, fset ? &gwf : nullptr));
-    if (fset)
-      DSTD_TRYH(finish_set(g.B, g.A, g.NN2, dA, gr->brm, dalpha, adjs, assign_dA, dW2, Amul, &wrf, &gwf, ws_s));
+    DSTD_TRYH(gemm(gw, ws_gs, ws_s, &gwf));
+    DSTD_TRYH(finish_set(g.B, g.A, g.NN2, dA, gr->brm, dalpha, adjs, assign_dA, dW2, Amul, &wrf, &gwf, ws_s));
     DSTD_TRYH(wg->release(slot));
   }
   // the three 1x1 convs at once: dx += Wp^T dG;  [dWp | dbp] = sum dG [x; 1]^T
@@ -937,10 +925,7 @@ int dstd_model_train_fwd_sync(const dstd_model_params* p, const float* x, int B,
   const size_t act = (size_t)B * C * T * V;
   // the blocks' second spatial ops build their adjacency on a second stream
   // (block_fwd); joined at each block and by the destructor on any return
-#ifndef DSTD_FWD_SIDE  // (A/B: 0 = the forward on the caller's stream only)
-#define DSTD_FWD_SIDE 1
-#endif
-  Wgrad side((flags & DSTD_TRAIN_ONE_STREAM) || !DSTD_FWD_SIDE ? nullptr : wgrad_acquire());
+  Wgrad side((flags & DSTD_TRAIN_ONE_STREAM) ? nullptr : wgrad_acquire());
   side.main = s;
   DSTD_TRY(prep_nctv(x, B, T, V, 3, S.X0, s));                                   // :298-303
   {  // every block's packed conv weights, kMaxCopyJobs per launch

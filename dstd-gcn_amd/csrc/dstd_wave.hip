@@ -736,16 +736,6 @@ int wave_occupancy(K k) {
   return nb;
 }
 
-// (compile-time only: a -DDSTD_NO_WAVE build routes the exact-fp32 block
-// launches to the generic kernels; no process-wide switch)
-bool wave_disabled() {
-#ifdef DSTD_NO_WAVE
-  return true;
-#else
-  return false;
-#endif
-}
-
 template <int V, int CIN, int COUT, bool RES>
 hipError_t spatial_wave_launch(const SpatialArgs& a, hipStream_t s) {
   static const int occ = wave_occupancy(k_spatial_wave<V, CIN, COUT, RES, true>);
@@ -789,7 +779,6 @@ hipError_t temporal_wave_run(const TemporalArgs& a, hipStream_t s) {
 }  // namespace
 
 hipError_t launch_spatial_wave(const SpatialArgs& a, hipStream_t s) {
-  if (wave_disabled()) return hipErrorNotSupported;
   if (a.NI != 2 || a.epi != 1) return hipErrorNotSupported;
   if (a.pq && (a.npqw != 2 || !pq_layout_eq(a.pql, pq_layout_tv(4, a.T, a.V)))) return hipErrorNotSupported;
   if (a.adj_ld % 4 != 0) return hipErrorNotSupported;
@@ -802,7 +791,6 @@ hipError_t launch_spatial_wave(const SpatialArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_temporal_wave(const TemporalArgs& a, hipStream_t s) {
-  if (wave_disabled()) return hipErrorNotSupported;
   if (a.V > 32) return hipErrorNotSupported;
   if (a.pq && (a.npqw != 4 || !pq_layout_eq(a.pql, pq_layout_vt(8, a.T, a.V)))) return hipErrorNotSupported;
   if (a.adj_ld % 4 != 0) return hipErrorNotSupported;

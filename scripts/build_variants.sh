@@ -1,7 +1,9 @@
 #!/bin/bash
 # Variant libraries for same-box A/B (scripts/ab_kernels.py): each NAME=DEFS
 # pair builds dstd-gcn_amd/libdstd_gcn_NAME.so from the current sources.
-#   scripts/build_variants.sh tf8=-DDSTD_TF_NW_H36M=8 sp3=-DDSTD_HL_WPE=3
+#   scripts/build_variants.sh stamps=-DDSTD_STAMPS
+# (DSTD_STAMPS is the only build switch; an experiment edits a constant in
+# csrc/ and builds it under a name: scripts/build_variants.sh try1=)
 cd "$(dirname "$0")/../dstd-gcn_amd" || exit 2
 for spec in "$@"; do
   name=${spec%%=*}; defs=${spec#*=}

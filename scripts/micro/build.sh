@@ -5,7 +5,7 @@ cd "$(dirname "$0")" || exit 2
   -L../../dstd-gcn_amd -ldstd_gcn -Wl,-rpath,'$ORIGIN/../../dstd-gcn_amd'
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 skinny_micro.cpp -o skinny_micro \
   -L../../dstd-gcn_amd -ldstd_gcn -Wl,-rpath,'$ORIGIN/../../dstd-gcn_amd'
-# the same benchmark against variant libraries: MICRO_VARIANTS="nostream csg2 ..."
+# the same benchmark against variant libraries: MICRO_VARIANTS="name1 name2 ..."
 # builds skinny_micro_<name> linked with libdstd_gcn_<name>.so
 for v in ${MICRO_VARIANTS:-}; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 skinny_micro.cpp -o skinny_micro_$v \

@@ -1,6 +1,6 @@
 // Is an LDS read's address VGPR consumed when the ds_read issues, or may a
 // VALU that overwrites it right afterwards change the address?  (Round-3
-// bisection of the DSTD_TF_HOISTW build of k_temporal_fused: its second row
+// bisection of k_temporal_fused with its W fragments hoisted: its second row
 // tile's W fragments were read by
 //   ds_read_b64 v[36:37], v16 ; ds_read_b64 v[38:39], v17 ; v_cndmask_b32 v16, 0, 1, s[8:9]
 // and only that row tile came out wrong.)

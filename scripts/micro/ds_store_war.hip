@@ -2,7 +2,7 @@
 // after the ds_write issues change the bytes written?
 //
 // Round-3 bisection of k_temporal_fused with the conv_rm W fragments hoisted
-// (dstd_hilo.hip, DSTD_TF_HOISTW): only the second row tile's planes were
+// (dstd_hilo.hip, today's default): only the second row tile's planes were
 // wrong, and the only code difference at their stores was
 //   v_add_u32_e32 v20, 0x15f00, v60
 //   ds_write_b64 v20, v[18:19]            (hi plane)

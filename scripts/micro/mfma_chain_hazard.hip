@@ -2,7 +2,7 @@
 // the wait states hipcc's hazard recognizer inserts (none, for all of these)?
 //
 // Found in round 3: k_temporal_fused with the conv_rm W fragments hoisted out
-// of its tile loop (dstd_hilo.hip, DSTD_TF_HOISTW) computed wrong planes for
+// of its tile loop (dstd_hilo.hip, today's default) computed wrong planes for
 // its second row tile only.  The compiler had emitted that tile's chain as
 //   v_mfma_f32_16x16x32_f16 v[48:51], v[16:19], v[12:15], 0
 //   v_mfma_f32_16x16x32_f16 v[20:23], v[20:23], v[8:11], v[48:51]   (C = previous D, new D = own A)

@@ -3,7 +3,7 @@
 // accumulator, against what hipcc inserts?
 //
 // Round-3 bisection of k_temporal_fused built with the conv_rm W fragments
-// hoisted out of its tile loop (dstd_hilo.hip, DSTD_TF_HOISTW, -> wrong
+// hoisted out of its tile loop (dstd_hilo.hip, today's default, -> wrong
 // planes for its second row tile): a plane dump showed that exactly the first
 // two of each lane's four accumulator values (acc[0], acc[1]) were wrong.
 // hipcc had emitted that row tile's conv_rm as a back-to-back chain
