@@ -84,6 +84,17 @@ class BnSyncStruct(ctypes.Structure):
                 ("buf", ctypes.c_void_p), ("buf_floats", ctypes.c_longlong)]
 
 
+class LossProblem(ctypes.Structure):
+    """include/dstd_gcn_loss.h dstd_loss_problem: pred [B][T][V][3] against targ
+    [B][targ_T][V][3], pred frame s <-> targ frame targ_t0 + targ_step * s."""
+    _fields_ = [("pred", ctypes.c_void_p), ("targ", ctypes.c_void_p), ("B", ctypes.c_int), ("T", ctypes.c_int),
+                ("V", ctypes.c_int), ("targ_T", ctypes.c_int), ("targ_t0", ctypes.c_int), ("targ_step", ctypes.c_int)]
+
+
+# include/dstd_gcn_loss.h DSTD_LOSS_*: term bits, slot k of a values / coef row is bit 1 << k
+LOSS_JL2, LOSS_TL2, LOSS_CL1, LOSS_CL2 = 1, 2, 4, 8
+LOSS_NTERMS = 4
+
 TRAIN_RUNNING_STATS = 1  # include/dstd_gcn_train.h DSTD_TRAIN_RUNNING_STATS
 TRAIN_PAIRED = 2  # DSTD_TRAIN_PAIRED: two BatchNorm batches of B/2 (a forward pair)
 TRAIN_SEED_DEVICE = 4  # DSTD_TRAIN_SEED_DEVICE: the dropout seed is read from device memory
@@ -221,6 +232,13 @@ def lib():
         L.dstd_mpjpe_bwd.argtypes = [vp, vp, sz, vp, f32, vp, vp]
         L.dstd_frame_mpjpe.restype = ci
         L.dstd_frame_mpjpe.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, vp, vp, ci, vp, vp]
+        # weighted / multi-term training loss (include/dstd_gcn_loss.h)
+        L.dstd_losses_workspace_bytes.restype = sz
+        L.dstd_losses_workspace_bytes.argtypes = []
+        L.dstd_losses_fwd.restype = ci
+        L.dstd_losses_fwd.argtypes = [ctypes.POINTER(LossProblem), ci, uf, vp, vp, vp, sz, vp]
+        L.dstd_losses_bwd.restype = ci
+        L.dstd_losses_bwd.argtypes = [ctypes.POINTER(LossProblem), ci, uf, vp, vp, f32, ctypes.POINTER(vp), vp]
         # non-refine ST_GCNN_layer branch (include/dstd_gcn_aux.h)
         L.dstd_ctg_workspace_bytes.restype = sz
         L.dstd_ctg_workspace_bytes.argtypes = [ci] * 4
@@ -254,6 +272,7 @@ TRAIN_EXPORTS = ("dstd_dstdgc_train_saved_bytes", "dstd_dstdgc_train_workspace_b
                  "dstd_debug_aggb_last")
 AUX_EXPORTS = ("dstd_ctg_workspace_bytes", "dstd_ctg_fwd", "dstd_ctg_bwd", "dstd_conv2d_workspace_bytes",
                "dstd_conv2d_fwd", "dstd_conv2d_bwd")
+LOSS_EXPORTS = ("dstd_losses_workspace_bytes", "dstd_losses_fwd", "dstd_losses_bwd")
 
 
 ARITHMETICS = ("split", "fp32")

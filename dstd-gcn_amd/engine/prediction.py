@@ -5,7 +5,11 @@ format as the reference, driving the MI355X model:
 
 * ``train`` (:198-317): train-mode forward (native, batch-statistics BN),
   mpjpe loss, the inverse-time augmentation pass, ``all_loss / 2``, native
-  backward, Adam step, StepLR at epoch end.  Losses accumulate on the GPU; the
+  backward, Adam step, StepLR at epoch end.  With joint weights
+  (``use_weight``) or other loss lines than one ``jl2`` (``tl2``, ``cl1``,
+  ``cl2``) every line of both passes is one native forward and one native
+  backward (engine/loss.py weighted_losses) reading the targets in place;
+  the weights are uploaded once per call.  Losses accumulate on the GPU; the
   epoch synchronises once when it reports its average.  Under
   ``torch.distributed`` (one process per GPU) gradients are averaged with one
   flat all-reduce per step (dstd_dist.allreduce_grads) and the reported
@@ -34,7 +38,7 @@ import torch.optim as optim
 
 import dstd_native as native
 
-from .loss import LOSSES, AccumLoss, DeviceAccum
+from .loss import LOSSES, AccumLoss, DeviceAccum, LossSpec, prepare_joint_weights, weighted_losses
 from .transform import TRANSFORMS
 
 
@@ -52,11 +56,19 @@ class ModelWrapper(nn.Module):
         for ls in loss.keys():
             name = loss[ls][0]
             if name not in LOSSES:
-                raise NotImplementedError(f"loss '{name}' is not built (shipped configs use jl2 only)")
+                raise NotImplementedError(f"loss '{name}' is not built (built: {', '.join(LOSSES)})")
             self.loss_funcs[ls] = (LOSSES[name], loss[ls][1])
             if ls in self.all_loss:
                 raise ValueError("Redundant Error", ls)
             self.all_loss.add(ls)
+        # every line in one native forward / backward (engine/loss.py weighted_losses) ...
+        self.loss_spec = LossSpec([(loss[ls][0], loss[ls][1]) for ls in loss.keys()])
+        # ... except the shipped configuration, one jl2 line, which without
+        # joint weights keeps the plain dstd_mpjpe_fwd / _bwd path
+        self.plain_mpjpe = [loss[ls][0] for ls in loss.keys()] == ["jl2"]
+
+    def fused_losses(self, wgts):
+        return not (self.plain_mpjpe and wgts is None)
 
     def forward(self, inputs, training=True):
         outputs = self.model(inputs)
@@ -67,6 +79,9 @@ class ModelWrapper(nn.Module):
     def calc_loss(self, pred, gt, loss_type="all", wgts=None):
         if loss_type != "all" and loss_type != "sum" and loss_type not in self.all_loss:
             raise ValueError(f"Invalid loss type {loss_type}")
+        if loss_type in ("all", "sum") and self.fused_losses(wgts):
+            out = weighted_losses(self.loss_spec, [pred], gt, None, wgts)[0]
+            return dict(zip(self.loss_funcs, out.unbind(0))) if loss_type == "all" else out.sum()
         if loss_type == "all":
             return {ls: w * fn(pred, gt, wgts) for ls, (fn, w) in self.loss_funcs.items()}
         if loss_type == "sum":
@@ -167,6 +182,7 @@ class PredictionEngine:
             optimizer = optim.Adam(params, lr=self.config["learn"]["lr"],
                                    weight_decay=self.config["learn"]["weight_decay"], fused=fused or None)
         self._graph_step = None
+        self._joint_weights, self._graph_weights_key = None, None
         scheduler = optim.lr_scheduler.StepLR(optimizer, step_size=self.config["learn"]["step_size"],
                                               gamma=self.config["learn"]["gamma"])
         return optimizer, scheduler
@@ -176,6 +192,17 @@ class PredictionEngine:
         dev = self.device
         t_l = {key_loss: DeviceAccum(dev) for key_loss in self.config["loss"]}
         self.model.train()
+        if weights is not None:
+            # checked and uploaded once per call, not per step: a step captured
+            # as a graph holds no host-to-device copy and replays read this buffer
+            # (the next call's weights are copied into the same buffer)
+            weights = self._joint_weights = prepare_joint_weights(weights, dev, into=self._joint_weights)
+        key = None if weights is None else weights.dev.data_ptr()
+        if self._graph_step is not None and key != self._graph_weights_key:
+            self._graph_step = None  # captured without joint weights, or with another buffer: capture again
+        self._graph_weights_key = key
+        if self.model.fused_losses(weights):
+            self.model.loss_spec.matrix(dev)
         # backward accumulates straight into .grad (dstd_native.grad_sink) for
         # this epoch's steps only: the flag is restored on the way out, so a
         # caller that later wraps the model (DDP reducer hooks, user hooks)
@@ -255,13 +282,8 @@ class PredictionEngine:
             outputs = scale_tsfm.inverse(outputs)
         if time_tsfm is not None:
             outputs = time_tsfm.inverse(outputs)
-        t = outputs.shape[1]
-        targets_l = targets[:, -t:] if t != targets.shape[1] else targets
-        loss = self.model.calc_loss(outputs, targets_l, "all", weights)
-        all_loss = 0
-        for ls in loss:
-            all_loss = all_loss + loss[ls]
-        if self.config["inverse"]:  # time-reversed augmentation pass (:267-287)
+
+        def inverse_outputs(inputs_inv):  # time-reversed augmentation pass (:267-287)
             if pair:
                 outputs_inv = self.inverse(out_pair[1])
             else:
@@ -269,17 +291,39 @@ class PredictionEngine:
                     inputs_inv = time_tsfm.transform(inputs_inv)
                 inputs_inv = self.transform(inputs_inv)
                 outputs_inv = self.inverse(self.model(inputs_inv, True))
-            targets_inv = targets.flip(1)
-            t = outputs_inv.shape[1]
-            targets_il = targets_inv[:, -t:] if t != targets_inv.shape[1] else targets_inv
             if time_tsfm is not None:
                 outputs_inv = time_tsfm.inverse(outputs_inv)
             if scale_tsfm is not None:
                 outputs_inv = scale_tsfm.inverse(outputs_inv)
-            loss_inv = self.model.calc_loss(outputs_inv, targets_il, "all", weights)
-            for ls in loss_inv:
-                all_loss = all_loss + loss_inv[ls]
-            all_loss = all_loss / 2
+            return outputs_inv
+
+        t = outputs.shape[1]
+        if self.model.fused_losses(weights):
+            # every loss line of both passes in one native forward / backward;
+            # the targets are read in place through the frame mapping:
+            # targets[:, -t:] is (T - t, +1), targets.flip(1)[:, -t:] is (t - 1, -1)
+            preds, maps = [outputs], [(targets.shape[1] - t, 1)]
+            if self.config["inverse"]:
+                preds.append(inverse_outputs(inputs_inv))
+                maps.append((preds[1].shape[1] - 1, -1))
+            out = weighted_losses(self.model.loss_spec, preds, targets, maps, weights)
+            all_loss = out.sum() / 2 if self.config["inverse"] else out.sum()
+            loss = dict(zip(self.config["loss"], out[0].unbind(0)))
+        else:
+            targets_l = targets[:, -t:] if t != targets.shape[1] else targets
+            loss = self.model.calc_loss(outputs, targets_l, "all", weights)
+            all_loss = 0
+            for ls in loss:
+                all_loss = all_loss + loss[ls]
+            if self.config["inverse"]:
+                outputs_inv = inverse_outputs(inputs_inv)
+                targets_inv = targets.flip(1)
+                t = outputs_inv.shape[1]
+                targets_il = targets_inv[:, -t:] if t != targets_inv.shape[1] else targets_inv
+                loss_inv = self.model.calc_loss(outputs_inv, targets_il, "all", weights)
+                for ls in loss_inv:
+                    all_loss = all_loss + loss_inv[ls]
+                all_loss = all_loss / 2
         self.optimizer.zero_grad()
         all_loss.backward()
         if distributed:
