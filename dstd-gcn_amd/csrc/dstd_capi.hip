@@ -313,19 +313,33 @@ void add_block_hl_jobs(HLList& l, const dstd_block_params* p, const BlockFold& f
   }
 }
 
-// One DSTDGCB on NTVC activations.  pq_s must already hold P/Q of x for the
-// block's two spatial DSTDGCs; the block's weight images (add_block_hl_jobs)
-// must be prepared when hl says so.
+// The arguments of one DSTDGCB's launches on NTVC activations (run_block
+// launches them one block at a time, the encoder chain packs a run of them
+// into one launch): aa / ta the adjacency launches, and where hl says so
+// their split-f16 forms ah / aht, the split GC kernels ha / ht and the next
+// block's spatial adjacency sn (tail.next_adj).
 // xmodel (conv_st_in of the model, split spatial only): the model input
 // [B][T][V][3]; the kernels build x6 and block-0's spatial P/Q from it, x is
 // not read.
-hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const BlockScratch& sc, int B, int T, int V,
-                     const float* x, float* h, float* y, const BlockTail& tail, hipStream_t s, Prof& pf,
-                     const BlockHL& hl, const float* xmodel = nullptr) {
-  const bool res = p->cin != p->cout;
-  const bool from_model = xmodel && hl.s && p->cin == 6;
+struct BlockArgs {
+  bool res, from_model, adj_launch;
+  AdjArgs aa, ta;
+  AdjHLArgs ah, aht, sn;
+  SpatialHLArgs ha;
+  TemporalHLArgs ht;
+};
+void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold& f, const BlockScratch& sc, int B, int T,
+                      int V, const float* x, float* h, float* y, const BlockTail& tail, const BlockHL& hl,
+                      const float* xmodel) {
+  A = BlockArgs{};
+  const bool res = A.res = p->cin != p->cout;
+  const bool from_model = A.from_model = xmodel && hl.s && p->cin == 6;
+  A.adj_launch = !hl.s_pre && !(hl.adj0 && from_model);
+  AdjArgs &aa = A.aa, &ta = A.ta;
+  AdjHLArgs &ah = A.ah, &aht = A.aht, &sn = A.sn;
+  SpatialHLArgs& ha = A.ha;
+  TemporalHLArgs& ht = A.ht;
   // (1) spatial adjacency for both graphs
-  AdjArgs aa{};
   aa.pq = sc.pq_s;
   aa.pql = pq_layout_vt(8, T, V);
   for (int g = 0; g < 2; ++g) {
@@ -357,10 +371,6 @@ hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const Block
     aa.out_sN = 2L * T * aa.ldo;
     aa.out_sG = (long)T * aa.ldo;
   }
-  hipError_t e = hipSuccess;
-  AdjHLArgs ah{};
-  const bool adj_launch = !hl.s_pre && !(hl.adj0 && from_model);
-  if (adj_launch) pf.begin(DSTD_KIND_ADJ_S, s);
   if (hl.s) {
     ah.pq = aa.pq;
     ah.pql = aa.pql;
@@ -386,16 +396,9 @@ hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const Block
         ah.mb[g][1] = p->conv_s[g].bm2;
       }
     }
-    // (s_pre: already in sc.adj_s, built by the previous block's temporal launch)
-    if (adj_launch) e = launch_adj_hl(ah, 0, T, V, s);
-  } else {
-    e = launch_adj(aa, s);
   }
-  if (adj_launch) pf.end(s);
-  if (e != hipSuccess) return e;
 
   // (2) spatial GC + bn + residual + prelu, P_t/Q_t of h
-  SpatialHLArgs ha{};
   if (hl.s) {
     ha.x = from_model ? xmodel : x;
     ha.xmodel = from_model ? 1 : 0;
@@ -427,9 +430,129 @@ hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const Block
     ha.pqb[0] = p->conv_t.bm1;
     ha.pqb[1] = p->conv_t.bm2;
     ha.pq = sc.pq_t;
+  }
+
+  // (3) temporal adjacency
+  ta.pq = sc.pq_t;
+  ta.pql = pq_layout_tv(4, T, V);
+  ta.p_ch[0] = 0;
+  ta.q_ch[0] = 2;
+  ta.W[0] = p->conv_t.wrm;
+  ta.bias[0] = p->conv_t.brm;
+  ta.astat[0] = f.astat_t;
+  ta.mode = 1;
+  ta.B = B;
+  ta.T = T;
+  ta.V = V;
+  ta.nrow = V;
+  ta.K = 2 * V;
+  ta.NA = T;
+  ta.ncol = T * T;
+  ta.ngroups = 1;
+  ta.alpha = p->alpha_tm;
+  ta.out = sc.adj_t;
+  ta.out_sG = 0;
+  if (hl.t) {  // split-f16 planes [B][V][2][T][SL]
+    ta.hl = 1;
+    ta.ncol = T * hl_sl_temporal(T);
+    ta.ldo = 2 * ta.ncol;
+    ta.out_sN = (long)V * ta.ncol;
+  } else {
+    ta.ldo = adj_ld_temporal(T);
+    ta.out_sN = (long)V * ta.ldo;
+  }
+  if (hl.t) {
+    aht.pq = ta.pq;
+    aht.pql = ta.pql;
+    aht.B = B;
+    aht.ngroups = 1;
+    aht.p_ch[0] = ta.p_ch[0];
+    aht.wimg[0] = f.hl_rmt;
+    aht.wscale[0] = hls(f, 7);
+    aht.bias[0] = f.hl_rbias + 2 * T;
+    aht.astat[0] = ta.astat[0];
+    aht.alpha = ta.alpha;
+    aht.out = reinterpret_cast<uint16_t*>(ta.out);
+    aht.out_sN = 2 * ta.out_sN;
+    aht.out_sG = 0;
+  }
+
+  // (4) temporal GC + tail epilogue (+ next block's spatial P/Q)
+  if (hl.t) {
+    ht.h = h;
+    ht.B = B;
+    ht.T = T;
+    ht.V = V;
+    ht.C = p->cout;
+    ht.adj = reinterpret_cast<const uint16_t*>(sc.adj_t);
+    ht.wimg = f.hl_wt;
+    ht.wscale = hls(f, 3);
+    ht.adjb = hls(f, 7);
+    ht.bf = p->conv_t.bf;
+    ht.epi = tail.epi;
+    ht.xres = tail.xres;
+    ht.bn_s = tail.bn_s;
+    ht.bn_h = tail.bn_h;
+    ht.prelu = tail.prelu;
+    ht.y = y;
+    if (tail.next) {
+      const dstd_block_params* q = tail.next;
+      ht.pqimg = f.hl_pqt;
+      ht.pqscale = hls(f, 4);
+      ht.pqb[0] = q->conv_s[0].bm1;
+      ht.pqb[1] = q->conv_s[0].bm2;
+      ht.pqb[2] = q->conv_s[1].bm1;
+      ht.pqb[3] = q->conv_s[1].bm2;
+      ht.pq = sc.pq_s;
+    }
+    // the next block's spatial adjacency (its launch_adj_hl mode 0 arguments)
+    if (tail.next_adj) {
+      const dstd_block_params* q = tail.next;
+      const BlockFold& nf = *tail.next_f;
+      const int ncol = V * hl_sl_spatial(V);
+      sn.pq = sc.pq_s;
+      sn.pql = pq_layout_vt(8, T, V);
+      sn.B = B;
+      sn.ngroups = 2;
+      for (int g = 0; g < 2; ++g) {
+        sn.p_ch[g] = 4 * g;
+        sn.wimg[g] = nf.hl_rms[g];
+        sn.wscale[g] = hls(nf, 5 + g);
+        sn.bias[g] = nf.hl_rbias + g * T;
+        sn.astat[g] = nf.astat_s + g * V * V;
+      }
+      sn.alpha = q->alpha_sm;
+      sn.out = reinterpret_cast<uint16_t*>(sc.adj_s);
+      sn.out_sG = 2L * T * ncol;  // halves
+      sn.out_sN = 2 * sn.out_sG;
+    }
+  }
+}
+
+// One DSTDGCB on NTVC activations.  pq_s must already hold P/Q of x for the
+// block's two spatial DSTDGCs; the block's weight images (add_block_hl_jobs)
+// must be prepared when hl says so.
+hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const BlockScratch& sc, int B, int T, int V,
+                     const float* x, float* h, float* y, const BlockTail& tail, hipStream_t s, Prof& pf,
+                     const BlockHL& hl, const float* xmodel = nullptr) {
+  BlockArgs A;
+  build_block_args(A, p, f, sc, B, T, V, x, h, y, tail, hl, xmodel);
+  const bool res = A.res;
+  // (1) spatial adjacency for both graphs
+  // (s_pre: already in sc.adj_s, built by the previous block's temporal launch)
+  hipError_t e = hipSuccess;
+  if (A.adj_launch) {
+    pf.begin(DSTD_KIND_ADJ_S, s);
+    e = hl.s ? launch_adj_hl(A.ah, 0, T, V, s) : launch_adj(A.aa, s);
+    pf.end(s);
+  }
+  if (e != hipSuccess) return e;
+
+  // (2) spatial GC + bn + residual + prelu, P_t/Q_t of h
+  if (hl.s) {
     if (!hl.bf) {  // (k_block_fused runs it with the temporal GC, step 4)
       pf.begin(DSTD_KIND_SPATIAL, s);
-      e = launch_spatial_hl(ha, s);
+      e = launch_spatial_hl(A.ha, s);
       pf.end(s);
       if (e != hipSuccess) return e;
     }
@@ -473,117 +596,24 @@ hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const Block
   }
 
   // (3) temporal adjacency
-  AdjArgs ta{};
-  ta.pq = sc.pq_t;
-  ta.pql = pq_layout_tv(4, T, V);
-  ta.p_ch[0] = 0;
-  ta.q_ch[0] = 2;
-  ta.W[0] = p->conv_t.wrm;
-  ta.bias[0] = p->conv_t.brm;
-  ta.astat[0] = f.astat_t;
-  ta.mode = 1;
-  ta.B = B;
-  ta.T = T;
-  ta.V = V;
-  ta.nrow = V;
-  ta.K = 2 * V;
-  ta.NA = T;
-  ta.ncol = T * T;
-  ta.ngroups = 1;
-  ta.alpha = p->alpha_tm;
-  ta.out = sc.adj_t;
-  ta.out_sG = 0;
-  if (hl.t) {  // split-f16 planes [B][V][2][T][SL]
-    ta.hl = 1;
-    ta.ncol = T * hl_sl_temporal(T);
-    ta.ldo = 2 * ta.ncol;
-    ta.out_sN = (long)V * ta.ncol;
-  } else {
-    ta.ldo = adj_ld_temporal(T);
-    ta.out_sN = (long)V * ta.ldo;
-  }
-  AdjHLArgs aht{};
-  if (hl.t) {
-    aht.pq = ta.pq;
-    aht.pql = ta.pql;
-    aht.B = B;
-    aht.ngroups = 1;
-    aht.p_ch[0] = ta.p_ch[0];
-    aht.wimg[0] = f.hl_rmt;
-    aht.wscale[0] = hls(f, 7);
-    aht.bias[0] = f.hl_rbias + 2 * T;
-    aht.astat[0] = ta.astat[0];
-    aht.alpha = ta.alpha;
-    aht.out = reinterpret_cast<uint16_t*>(ta.out);
-    aht.out_sN = 2 * ta.out_sN;
-    aht.out_sG = 0;
-  }
   if (!hl.tf) {  // the fused temporal kernel builds its adjacency itself
     pf.begin(DSTD_KIND_ADJ_T, s);
-    e = hl.t ? launch_adj_hl(aht, 1, T, V, s) : launch_adj(ta, s);
+    e = hl.t ? launch_adj_hl(A.aht, 1, T, V, s) : launch_adj(A.ta, s);
     pf.end(s);
     if (e != hipSuccess) return e;
   }
 
   // (4) temporal GC + tail epilogue (+ next block's spatial P/Q)
   if (hl.t) {
-    TemporalHLArgs ht{};
-    ht.h = h;
-    ht.B = B;
-    ht.T = T;
-    ht.V = V;
-    ht.C = p->cout;
-    ht.adj = reinterpret_cast<const uint16_t*>(sc.adj_t);
-    ht.wimg = f.hl_wt;
-    ht.wscale = hls(f, 3);
-    ht.adjb = hls(f, 7);
-    ht.bf = p->conv_t.bf;
-    ht.epi = tail.epi;
-    ht.xres = tail.xres;
-    ht.bn_s = tail.bn_s;
-    ht.bn_h = tail.bn_h;
-    ht.prelu = tail.prelu;
-    ht.y = y;
-    if (tail.next) {
-      const dstd_block_params* q = tail.next;
-      ht.pqimg = f.hl_pqt;
-      ht.pqscale = hls(f, 4);
-      ht.pqb[0] = q->conv_s[0].bm1;
-      ht.pqb[1] = q->conv_s[0].bm2;
-      ht.pqb[2] = q->conv_s[1].bm1;
-      ht.pqb[3] = q->conv_s[1].bm2;
-      ht.pq = sc.pq_s;
-    }
-    // the next block's spatial adjacency (its launch_adj_hl mode 0 arguments)
-    AdjHLArgs sn{};
-    if (tail.next_adj) {
-      const dstd_block_params* q = tail.next;
-      const BlockFold& nf = *tail.next_f;
-      const int ncol = V * hl_sl_spatial(V);
-      sn.pq = sc.pq_s;
-      sn.pql = pq_layout_vt(8, T, V);
-      sn.B = B;
-      sn.ngroups = 2;
-      for (int g = 0; g < 2; ++g) {
-        sn.p_ch[g] = 4 * g;
-        sn.wimg[g] = nf.hl_rms[g];
-        sn.wscale[g] = hls(nf, 5 + g);
-        sn.bias[g] = nf.hl_rbias + g * T;
-        sn.astat[g] = nf.astat_s + g * V * V;
-      }
-      sn.alpha = q->alpha_sm;
-      sn.out = reinterpret_cast<uint16_t*>(sc.adj_s);
-      sn.out_sG = 2L * T * ncol;  // halves
-      sn.out_sN = 2 * sn.out_sG;
-    }
     if (hl.bf) {
       pf.begin(DSTD_KIND_BLOCK, s);
-      e = launch_block_fused(ha, ht, aht, tail.next_adj ? &sn : nullptr, s, hl.adj0 && from_model ? &ah : nullptr);
+      e = launch_block_fused(A.ha, A.ht, A.aht, tail.next_adj ? &A.sn : nullptr, s,
+                             hl.adj0 && A.from_model ? &A.ah : nullptr);
       pf.end(s);
       return e;
     }
     pf.begin(DSTD_KIND_TEMPORAL, s);
-    e = hl.tf ? launch_temporal_fused(ht, aht, tail.next_adj ? &sn : nullptr, s) : launch_temporal_hl(ht, s);
+    e = hl.tf ? launch_temporal_fused(A.ht, A.aht, tail.next_adj ? &A.sn : nullptr, s) : launch_temporal_hl(A.ht, s);
     pf.end(s);
     return e;
   }
@@ -848,7 +878,8 @@ int dstd_block_fwd(const dstd_block_params* p, const float* x, int B, int T, int
 int dstd_block_fwd_ex(const dstd_block_params* p, const float* x, int B, int T, int V, float* y, void* workspace,
                       size_t workspace_bytes, void* stream, unsigned flags) {
   StreamDeviceGuard dev_guard_(stream, x);
-  if (flags & ~(DSTD_FWD_EXACT_FP32 | DSTD_FWD_FUSED_TEMPORAL | DSTD_FWD_SEPARATE_BLOCK)) return DSTD_EINVAL;
+  if (flags & ~(DSTD_FWD_EXACT_FP32 | DSTD_FWD_FUSED_TEMPORAL | DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS))
+    return DSTD_EINVAL;
   if (!x || !y || !workspace || !block_ok(p) || !shape_ok(B, T, V)) return DSTD_EINVAL;
   if (!limits_ok(T, V, p->cin, p->cout)) return DSTD_ELIMIT;
   if (workspace_bytes < dstd_block_workspace_bytes(B, p->cin, p->cout, T, V)) return DSTD_EWORKSPACE;
@@ -887,7 +918,7 @@ int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* 
   StreamDeviceGuard dev_guard_(stream, x);
   const bool reuse = (flags & DSTD_FWD_REUSE_CONSTANTS) != 0;
   if (flags & ~(DSTD_FWD_REUSE_CONSTANTS | DSTD_FWD_EXACT_FP32 | DSTD_FWD_SEPARATE_ADJ | DSTD_FWD_FUSED_TEMPORAL |
-                DSTD_FWD_SEPARATE_BLOCK))
+                DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS))
     return DSTD_EINVAL;
   if (!p || !x || !y || !workspace) return DSTD_EINVAL;
   if (prof && (prof->capacity < 0 || (prof->capacity > 0 && (!prof->events || !prof->kinds)))) return DSTD_EINVAL;
@@ -1014,10 +1045,32 @@ int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* 
     DSTD_TRY(run_hl_prep(hj, s));
     pf.end(s);
   }
-  for (int b = 0; b < NB; ++b) {
+  // A run of consecutive encoder blocks as one launch (k_enc_chain): blocks
+  // that would each run k_block_fused on planes from the previous launch.
+  // Not in a profiled call: its event brackets are per block.
+  const bool chain = !(flags & (DSTD_FWD_SEPARATE_ENCODERS | DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ADJ)) &&
+                     !(prof && prof->capacity > 0) && enc_chain_supported(T, V);
+  auto chain_block = [&](int b, EncChainArgs* c) {
+    if (!chain || b < 1 || b > L_ || !hls[b].bf || !hls[b].s_pre || !tails[b].next_adj) return false;
+    BlockArgs A;
+    build_block_args(A, blk[b], *fold[b], L.sc, B, T, V, xin[b], hbuf[b], ybuf[b], tails[b], hls[b], nullptr);
+    BlockFusedArgs ba;
+    return block_fused_args(A.ha, A.ht, A.aht, &A.sn, &ba, nullptr) == hipSuccess &&
+           enc_chain_append(c, ba) == hipSuccess;
+  };
+  for (int b = 0; b < NB;) {
+    EncChainArgs c{};
+    int e = b;
+    while (e < NB && chain_block(e, &c)) ++e;
+    if (e - b >= 2) {
+      DSTD_TRY(launch_enc_chain(c, s));
+      b = e;
+      continue;
+    }
     pf.block = b;
     DSTD_TRY(run_block(blk[b], *fold[b], L.sc, B, T, V, xin[b], hbuf[b], ybuf[b], tails[b], s, pf, hls[b],
                        b == 0 ? x : nullptr));
+    ++b;
   }
   return DSTD_OK;
 }

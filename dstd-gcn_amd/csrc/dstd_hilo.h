@@ -385,5 +385,117 @@ hipError_t launch_block_fused(const SpatialHLArgs& sa, const TemporalHLArgs& g, 
 hipError_t block_fused_args(const SpatialHLArgs& sa, const TemporalHLArgs& g, const AdjHLArgs& j, const AdjHLArgs* sn,
                             BlockFusedArgs* out, const AdjHLArgs* s0 = nullptr);
 
+// ---- a run of consecutive encoder blocks as one launch (k_enc_chain) ------
+// One workgroup per sample runs block_fused_body<64, 64, ENC> for every block
+// of the run in turn.  A BlockFusedArgs is ~1 KB
+// and kernel arguments end at 4 KB, so the launch carries the first block's
+// spatial / temporal arguments as the shared geometry (shapes, the P/Q and
+// plane scratch and their layouts, which every encoder block shares) and, per
+// block, only what differs between encoder blocks: the activation buffers of
+// the rotation and the block's weight images, scales, biases and tables.
+struct EncChainDesc {
+  // spatial GC (SpatialHLArgs)
+  const float* x;
+  float* h;  // SpatialHLArgs::y == TemporalHLArgs::h
+  const uint4* s_wimg[2];
+  const float* s_wscale[2];
+  const float* s_bf[2];
+  const float* s_bn_s;
+  const float* s_bn_h;
+  const float* s_prelu;
+  const float* s_adjb[2];
+  const uint4* s_pqimg;
+  const float* s_pqscale;
+  const float* s_pqb[2];
+  // temporal GC (TemporalHLArgs)
+  const uint4* t_wimg;
+  const float* t_wscale;
+  const float* t_bf;
+  const float* t_adjb;
+  const float* t_xres;
+  const float* t_bn_s;
+  const float* t_bn_h;
+  const float* t_prelu;
+  float* y;
+  const uint4* t_pqimg;
+  const float* t_pqscale;
+  const float* t_pqb[4];
+  // temporal adjacency (TemporalFusedArgs::j)
+  const uint4* j_wimg;
+  const float* j_wscale;
+  const float* j_bias;
+  const float* j_astat;
+  const float* j_alpha;
+  // the next block's spatial adjacency (TemporalFusedArgs::sn)
+  const uint4* n_wimg[2];
+  const float* n_wscale[2];
+  const float* n_bias[2];
+  const float* n_astat[2];
+  const float* n_alpha;
+};
+constexpr int kEncChainMax = 8;  // blocks per launch (longer encoder stacks: several launches)
+struct EncChainArgs {
+  SpatialHLArgs s;      // shared geometry: the first block's arguments
+  TemporalFusedArgs t;
+  int nblk;
+  EncChainDesc enc[kEncChainMax];
+};
+static_assert(sizeof(EncChainArgs) <= 4096, "kernel arguments end at 4 KB");
+// block i's arguments from the shared geometry and its descriptor
+__host__ __device__ inline void enc_chain_apply(const EncChainDesc& d, SpatialHLArgs& s) {
+  s.x = d.x;
+  s.y = d.h;
+  for (int g = 0; g < 2; ++g) {
+    s.wimg[g] = d.s_wimg[g];
+    s.wscale[g] = d.s_wscale[g];
+    s.bf[g] = d.s_bf[g];
+    s.adjb[g] = d.s_adjb[g];
+    s.pqb[g] = d.s_pqb[g];
+  }
+  s.bn_s = d.s_bn_s;
+  s.bn_h = d.s_bn_h;
+  s.prelu = d.s_prelu;
+  s.pqimg = d.s_pqimg;
+  s.pqscale = d.s_pqscale;
+}
+__host__ __device__ inline void enc_chain_apply(const EncChainDesc& d, TemporalHLArgs& g) {
+  g.h = d.h;
+  g.wimg = d.t_wimg;
+  g.wscale = d.t_wscale;
+  g.bf = d.t_bf;
+  g.adjb = d.t_adjb;
+  g.xres = d.t_xres;
+  g.bn_s = d.t_bn_s;
+  g.bn_h = d.t_bn_h;
+  g.prelu = d.t_prelu;
+  g.y = d.y;
+  g.pqimg = d.t_pqimg;
+  g.pqscale = d.t_pqscale;
+  for (int i = 0; i < 4; ++i) g.pqb[i] = d.t_pqb[i];
+}
+__host__ __device__ inline void enc_chain_apply_j(const EncChainDesc& d, AdjHLArgs& j) {
+  j.wimg[0] = d.j_wimg;
+  j.wscale[0] = d.j_wscale;
+  j.bias[0] = d.j_bias;
+  j.astat[0] = d.j_astat;
+  j.alpha = d.j_alpha;
+}
+__host__ __device__ inline void enc_chain_apply_sn(const EncChainDesc& d, AdjHLArgs& sn) {
+  for (int g = 0; g < 2; ++g) {
+    sn.wimg[g] = d.n_wimg[g];
+    sn.wscale[g] = d.n_wscale[g];
+    sn.bias[g] = d.n_bias[g];
+    sn.astat[g] = d.n_astat[g];
+  }
+  sn.alpha = d.n_alpha;
+}
+bool enc_chain_supported(int T, int V);
+// appends one validated encoder block (block_fused_args) to the run; the first
+// one sets the shared geometry.  hipErrorNotSupported when the block is no
+// 64 -> 64 ENC block with phase 3, differs from the run in anything but its
+// descriptor, or the run is full: the caller launches it on its own instead
+hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a);
+hipError_t launch_enc_chain(const EncChainArgs& c, hipStream_t s);
+
 
 }  // namespace dstd

@@ -366,9 +366,38 @@ struct SpatialStage {
   int rng[3];
 };
 
+// The members of the spatial arguments that the stage indexes by lane.  From
+// the launch's own argument struct that is an indexed load from the argument
+// segment; SpatialHLArgsVal marks a copy that lives in registers
+// (k_enc_chain's per-phase copy of block b's arguments), where an index would
+// put the whole struct into scratch: selects instead.
+struct SpatialHLArgsVal : SpatialHLArgs {};
+__device__ __forceinline__ uint4 arg_wimg(const SpatialHLArgs& a, int g, int i) { return a.wimg[g][i]; }
+__device__ __forceinline__ float arg_bf(const SpatialHLArgs& a, int g, int i) { return a.bf[g][i]; }
+__device__ __forceinline__ float arg_pqb(const SpatialHLArgs& a, int g, int i) { return a.pqb[g][i]; }
+// (the pointers pass through an empty asm, as TemporalStageLoad's: hipcc
+// otherwise turns the selects back into one indexed load; loads of native
+// vectors from global pointers: a uint4 copied through a generic pointer is a
+// memcpy that keeps the destination array in scratch)
+template <typename E>
+__device__ __forceinline__ E arg_pick_ld(const void* p0, const void* p1, const void* p2, int g, int i) {
+  asm volatile("" : "+s"(p0), "+s"(p1), "+s"(p2));
+  typedef __attribute__((address_space(1))) const E gE;
+  return ((gE*)(g == 0 ? p0 : g == 1 ? p1 : p2))[i];
+}
+__device__ __forceinline__ uint4 arg_wimg(const SpatialHLArgsVal& a, int g, int i) {
+  return __builtin_bit_cast(uint4, arg_pick_ld<u32x4>(a.wimg[0], a.wimg[1], a.wimg[2], g, i));
+}
+__device__ __forceinline__ float arg_bf(const SpatialHLArgsVal& a, int g, int i) {
+  return arg_pick_ld<float>(a.bf[0], a.bf[1], a.bf[2], g, i);
+}
+__device__ __forceinline__ float arg_pqb(const SpatialHLArgsVal& a, int g, int i) {
+  return arg_pick_ld<float>(a.pqb[0], a.pqb[1], a.pqb[1], g, i);
+}
+
 // every global load before the first LDS write (one memory round trip)
-template <int V, int CIN, int COUT, int NTH>
-__device__ __forceinline__ void stage_spatial(const SpatialHLArgs& a, SpatialStage<V, CIN, COUT>& st, int tid) {
+template <int V, int CIN, int COUT, int NTH, typename SA>
+__device__ __forceinline__ void stage_spatial(const SA& a, SpatialStage<V, CIN, COUT>& st, int tid) {
   using S = SpatialStage<V, CIN, COUT>;
   constexpr bool RES = S::RES;
   constexpr int NCT = S::NCT, WIMG = S::WIMG, PIMG = S::PIMG, NIMG = (RES ? 3 : 2) * WIMG;
@@ -379,7 +408,7 @@ __device__ __forceinline__ void stage_spatial(const SpatialHLArgs& a, SpatialSta
 #pragma unroll
   for (int it = 0; it < NW; ++it) {
     const int i = min(tid + it * NTH, NIMG - 1);
-    wv[it] = a.wimg[i / WIMG][i % WIMG];
+    wv[it] = arg_wimg(a, i / WIMG, i % WIMG);
   }
 #pragma unroll
   for (int it = 0; it < NP; ++it) pv[it] = a.pqimg[min(tid + it * NTH, PIMG - 1)];
@@ -401,7 +430,7 @@ __device__ __forceinline__ void stage_spatial(const SpatialHLArgs& a, SpatialSta
     }
   const int nbf = (RES ? 3 : 2) * 16 * NCT;
   static_assert((RES ? 3 : 2) * 16 * NCT <= NTH, "one conv bias per thread");
-  const float bf = tid < nbf && tid % (16 * NCT) < COUT ? a.bf[tid / (16 * NCT)][tid % (16 * NCT)] : 0.f;
+  const float bf = tid < nbf && tid % (16 * NCT) < COUT ? arg_bf(a, tid / (16 * NCT), tid % (16 * NCT)) : 0.f;
 #pragma unroll
   for (int it = 0; it < NW; ++it) {
     const int i = tid + it * NTH;
@@ -421,7 +450,7 @@ __device__ __forceinline__ void stage_spatial(const SpatialHLArgs& a, SpatialSta
       }
     }
   if (tid < nbf) st.bfl[tid / (16 * NCT)][tid % (16 * NCT)] = bf;
-  if (tid < 4) st.bql[tid] = a.pqb[tid >> 1][tid & 1];
+  if (tid < 4) st.bql[tid] = arg_pqb(a, tid >> 1, tid & 1);
   if (tid == 0) {
     st.scl[0] = *a.wscale[0];
     st.scl[1] = *a.wscale[1];
@@ -443,8 +472,8 @@ struct NoPQSink {
   __device__ int operator()(int, int, float, float, float, float) const { return 0; }
 };
 template <int V, int CIN, int COUT, typename AdjLoad, bool LATE_RES = false, typename PQSink = NoPQSink>
-__device__ __forceinline__ int spatial_units(const SpatialHLArgs& a, const SpatialStage<V, CIN, COUT>& st, int u,
-                                             int uend, int ustep, AdjLoad load_adj_g, PQSink pq_sink = {}) {
+__device__ __forceinline__ int spatial_units(const SpatialHLArgs& a, const SpatialStage<V, CIN, COUT>& st, const int tid,
+                                             int u, int uend, int ustep, AdjLoad load_adj_g, PQSink pq_sink = {}) {
   int bad = 0;
   using SM = SlotMap<V, true>;
   constexpr bool RES = CIN != COUT;
@@ -453,7 +482,7 @@ __device__ __forceinline__ int spatial_units(const SpatialHLArgs& a, const Spati
   constexpr int NCT = cdiv(COUT, 16);  // output channel tiles
   constexpr int KSO = cdiv(NCT, 2);    // P/Q k-steps
   static_assert(SM::MT == 2 && SM::NS == 1, "one K-step of two tiles per frame");
-  const int lane = threadIdx.x & 63;
+  const int lane = tid & 63;
   const int kl = lane >> 4, cl = lane & 15;
   const int T = a.T;
   const int efb = __builtin_amdgcn_readfirstlane(st.rng[0]), eb = __builtin_amdgcn_readfirstlane(st.rng[1]);
@@ -792,7 +821,7 @@ __global__ __launch_bounds__(spatial_nt()) __attribute__((amdgpu_waves_per_eu(kS
   };
   int uend;
   const int u = unit_range(a.B * T, uend);
-  spatial_units<V, CIN, COUT>(a, st, u, uend, 1, load_adj_g);
+  spatial_units<V, CIN, COUT>(a, st, threadIdx.x, u, uend, 1, load_adj_g);
 }
 
 // ===========================================================================
@@ -963,8 +992,8 @@ __host__ __device__ constexpr bool tf_res_acc(int T, int V) { return (T == 35 &&
 // each unit loads its own rows first (for more waves per SIMD instead)
 template <int T, int EPI, int C, int VB, bool LAZY, typename AdjLoad, bool PF = true, bool RA = false,
           int NUTC = cdiv(T, 16)>
-__device__ __forceinline__ void temporal_units(const TemporalHLArgs& a, const TemporalStage<T, EPI, C, VB>& st, int u,
-                                               int uend, int ustep, AdjLoad load_adj, int ut0 = 0) {
+__device__ __forceinline__ void temporal_units(const TemporalHLArgs& a, const TemporalStage<T, EPI, C, VB>& st, const int tid,
+                                               int u, int uend, int ustep, AdjLoad load_adj, int ut0 = 0) {
   // NUTC / ut0: the u tiles ut0 .. ut0 + NUTC - 1 of each unit (a u chunk of
   // k_temporal_fused at T = 75; every tile otherwise); load_adj fills
   // [NUTC] fragments for them
@@ -979,7 +1008,7 @@ __device__ __forceinline__ void temporal_units(const TemporalHLArgs& a, const Te
   const float* bfl = st.bfl;
   const float* bql = st.bql;
   const float* scl = st.scl;
-  const int lane = threadIdx.x & 63;
+  const int lane = tid & 63;
   const int kl = lane >> 4, cl = lane & 15;
   const int V = a.V;
   const bool has_pq = a.pq != nullptr;
@@ -1375,9 +1404,9 @@ __global__ __launch_bounds__((temporal_nt<T, C>())) __attribute__((amdgpu_waves_
         bo[ut] = bldu4(rl, off);
       }
     };
-    temporal_units<T, EPI, C, 32, true, decltype(load_adj_s), true, RA>(a, st, u0, uend, 1, load_adj_s);
+    temporal_units<T, EPI, C, 32, true, decltype(load_adj_s), true, RA>(a, st, threadIdx.x, u0, uend, 1, load_adj_s);
   } else {
-    temporal_units<T, EPI, C, 32, false, decltype(load_adj), true, RA>(a, st, u0, uend, 1, load_adj);
+    temporal_units<T, EPI, C, 32, false, decltype(load_adj), true, RA>(a, st, threadIdx.x, u0, uend, 1, load_adj);
   }
 }
 
@@ -1866,7 +1895,7 @@ struct SAdjStatic {
 // XIN: the P/Q from the model input (j.xin, conv_st_in's conv_m1/m2 rows
 // j.mw / j.mb, as k_adj_hl<0> forms them) instead of j.pq
 template <int T, int V, int NT, bool XIN = false>
-__device__ __forceinline__ void spatial_adj_sample(const AdjHLArgs& j, int n, unsigned char* dsm) {
+__device__ __forceinline__ void spatial_adj_sample(const AdjHLArgs& j, int n, unsigned char* dsm, const int tid) {
   using Gm = SAdjGeom<T, V>;
   using SM = typename Gm::SM;
   using EF = typename Gm::EF;
@@ -1878,7 +1907,7 @@ __device__ __forceinline__ void spatial_adj_sample(const AdjHLArgs& j, int n, un
   auto asg = [&](int g) { return reinterpret_cast<float*>(dsm + 2 * Gm::EFB + g * Gm::AS); };  // alq: + ASQ
   uint4* wl = reinterpret_cast<uint4*>(dsm + 2 * (Gm::EFB + Gm::AS));  // both images, graph-major
   float* bl = reinterpret_cast<float*>(dsm + 2 * (Gm::EFB + Gm::AS + Gm::WB));  // [g][16 RT]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kg = lane >> 4, cl = lane & 15;
 
   // ---- prologue: both graphs' P/Q -> E/F rows, conv_rm images, Astat, bias;
@@ -2125,6 +2154,21 @@ constexpr int kTfWavesH36M = 12;
 template <int T, int V>
 constexpr int tf_waves() { return T == 35 && V == 22 ? kTfWavesH36M : 8; }
 
+// How the fused bodies get at their arguments: accessors called where a phase
+// begins.  Here the launch's own argument structs; k_enc_chain's block b:
+// EncChainArgsAt below.
+struct BlockArgsRef {
+  const SpatialHLArgs* s_;
+  const TemporalFusedArgs* t_;
+  const AdjHLArgs* s0_;
+  __device__ __forceinline__ const SpatialHLArgs& s() const { return *s_; }
+  __device__ __forceinline__ const TemporalHLArgs& tg() const { return t_->g; }
+  __device__ __forceinline__ const AdjHLArgs& tj() const { return t_->j; }
+  __device__ __forceinline__ const AdjHLArgs& tsn() const { return t_->sn; }
+  __device__ __forceinline__ const AdjHLArgs& s0() const { return *s0_; }
+  __device__ __forceinline__ static constexpr uint32_t zero() { return 0u; }
+};
+
 // The body of k_temporal_fused for sample n on the workgroup's dynamic LDS
 // dsm (TFusedGeom::LDS bytes): the kernel below runs it once, k_block_fused
 // after the sample's spatial GC.
@@ -2135,20 +2179,18 @@ constexpr int tf_waves() { return T == 35 && V == 22 ? kTfWavesH36M : 8; }
 // stage lives), each wave right after its last spatial unit.  The same values
 // and places as tfused_body's own prologue writes.
 template <int T, int V, int EPI, int C>
-__device__ __forceinline__ void tfused_pre(const TemporalFusedArgs& fa, unsigned char* dsm) {
+__device__ __forceinline__ void tfused_pre(const AdjHLArgs& j, unsigned char* dsm, const int tid) {
   using Gm = TFusedGeom<T, V, EPI, C>;
   using SM = typename Gm::SM;
   using EF = typename Gm::EF;
   constexpr int NS = Gm::NS, TAIL = Gm::TAIL, KP = Gm::KP, K = Gm::K, SL = Gm::SL, NCOL = Gm::NCOL;
   constexpr int RTC = Gm::RTC, WIMG = Gm::WIMG, NT = 64 * tf_waves<T, V>(), NFR = Gm::NFR;
-  const AdjHLArgs& j = fa.j;
   float* El = reinterpret_cast<float*>(dsm + Gm::PLANES);
   float* Fl = El + Gm::EFE;
   uint4* wl = reinterpret_cast<uint4*>(Fl + Gm::EFF);
   float* asq = reinterpret_cast<float*>(wl + WIMG);
   float* alq = asq + Gm::ASQ;
   float* bsl = alq + Gm::ASQ;
-  const int tid = threadIdx.x;
   constexpr int FULL = NS * 2 * 64;
   constexpr int NWF = cdiv(RTC * FULL, NT), NWT = TAIL ? cdiv(RTC * 64, NT) : 0, NAS = cdiv(Gm::ASQ, NT);
   uint4 wf[NWF], wt[NWT > 0 ? NWT : 1];
@@ -2197,8 +2239,8 @@ __device__ __forceinline__ void tfused_pre(const TemporalFusedArgs& fa, unsigned
 // F rows by the spatial units (pq_sink), the pads, conv_rm rows, tables and
 // bias by tfused_pre before the workgroup barrier whose OR of the range flags
 // is sep_pre -- so phase 1 starts with its tiles
-template <int T, int V, int EPI, int C, bool PRE = false>
-__device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const int n, unsigned char* dsm,
+template <int T, int V, int EPI, int C, bool PRE = false, typename Args>
+__device__ __forceinline__ void tfused_body(const Args& fa, const int n, unsigned char* dsm, const int tid,
                                             const bool sep_pre = true) {
   using Gm = TFusedGeom<T, V, EPI, C>;
   using SM = typename Gm::SM;
@@ -2207,8 +2249,6 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
   constexpr int RC = Gm::RC, RTC = Gm::RTC, PJ = Gm::PJ, WIMG = Gm::WIMG, NW = tf_waves<T, V>(), NT = 64 * NW;
   constexpr int UF = Gm::UF, NUTC = Gm::NUTC, NFR = Gm::NFR;  // frames / u tiles per chunk, F rows
   constexpr float C2 = 2.8853900817779268f;       // 2*log2(e)
-  const TemporalHLArgs& a = fa.g;
-  const AdjHLArgs& j = fa.j;
   _Float16* planes = reinterpret_cast<_Float16*>(dsm);
   unsigned char* un = dsm + Gm::PLANES;  // phase-1 scratch / phase-2 stage (union)
   float* El = reinterpret_cast<float*>(un);
@@ -2225,7 +2265,7 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
   // wave index through readfirstlane: wave-uniform to the compiler, so the
   // unit indices derived from it live in SGPRs (as tid >> 6 they took ~24
   // VGPRs more and spilled)
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kg = lane >> 4, cl = lane & 15;
   if constexpr (C == 64) { TLH(3, 0) TLH(4, 0) }
   // (no static priority for the younger waves here, unlike k_spatial_hl:
@@ -2237,6 +2277,7 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
       const int jc = ch % Gm::NJCH, uc = ch / Gm::NJCH;
       const int v0 = jc * RC, nv = min(RC, V - v0), rt0 = jc * RTC, u0 = uc * UF;
       if (ch) __syncthreads();  // the previous chunk's phase 2 is done with the planes and the stage
+      decltype(auto) j = fa.tj();
       // ---- phase 1 prologue: P/Q -> E/F rows, the chunk's conv_rm rows, Astat, bias ----
       const PQLayout L = j.pql;
       const float* pqb = j.pq + (size_t)n * L.sn + j.p_ch[0];
@@ -2256,7 +2297,8 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
       bool sep;
       if (PRE && ch == 0) {
         // (the planes region held the spatial stage until the barrier: the pads now)
-        if (tid < Gm::jn(RC)) *reinterpret_cast<uint4*>(planes + tid * PJ + Gm::ZPAD) = make_uint4(0u, 0u, 0u, 0u);
+        const uint32_t z = fa.zero();
+        if (tid < Gm::jn(RC)) *reinterpret_cast<uint4*>(planes + tid * PJ + Gm::ZPAD) = make_uint4(z, z, z, z);
         sep = sep_pre;
       } else {
       ef_pad(1.f);
@@ -2491,6 +2533,7 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
       }
       // the phase-2 stage's loads now, its LDS writes after the barrier
       // (both after it, as before round 6: within +-0.2%)
+      decltype(auto) a = fa.tg();
       TemporalStageLoad<T, EPI, C, V, NT> stl;
       stl.load(a, tid, Gm::NCHUNK > 1 ? opaque_zero() : 0);
       __syncthreads();  // planes complete; the phase-1 scratch is free
@@ -2522,17 +2565,18 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
         }
       };
       temporal_units<T, EPI, C, V, true, decltype(load_adj), (NW <= 8 && !Gm::UCH), tf_res_acc(T, V), NUTC>(
-          a, st, ub + wave, ub + nv, NW, load_adj, u0 / 16);
+          a, st, tid, ub + wave, ub + nv, NW, load_adj, u0 / 16);
     }
   }
   // ---- phase 3: the next block's spatial adjacency planes of this sample
   // (where its scratch fits the launch's LDS: not at T = 75) ----
   if constexpr (C == 64 && tf_phase3<T, V>()) {
     TLH(3, 2)
-    if (fa.sn.out) {
+    decltype(auto) sn = fa.tsn();
+    if (sn.out) {
       __syncthreads();  // every unit's P/Q written (one CU: the workgroup-scope fences of the barrier suffice)
       TLH(2, 0)
-      spatial_adj_sample<T, V, NT>(fa.sn, n, dsm);
+      spatial_adj_sample<T, V, NT>(sn, n, dsm, tid);
     }
     TLH(3, 3)
   }
@@ -2541,7 +2585,7 @@ __device__ __forceinline__ void tfused_body(const TemporalFusedArgs& fa, const i
 template <int T, int V, int EPI, int C>
 __global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_waves_per_eu((tf_waves<T, V>() / 4), (tf_waves<T, V>() / 4)))) void k_temporal_fused(TemporalFusedArgs fa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
-  tfused_body<T, V, EPI, C>(fa, blockIdx.x, dsm);  // one sample per workgroup
+  tfused_body<T, V, EPI, C>(BlockArgsRef{nullptr, &fa, nullptr}, blockIdx.x, dsm, threadIdx.x);  // one sample per workgroup
 }
 
 // ===========================================================================
@@ -2563,9 +2607,8 @@ struct BlockFusedGeom {
   static_assert(LDS <= kLdsBudget, "LDS");
 };
 
-template <int T, int V, int CIN, int COUT, int EPI>
-__device__ __forceinline__ void block_fused_body(const SpatialHLArgs& sa, const TemporalFusedArgs& ta, const AdjHLArgs& s0,
-                                                 const int n, unsigned char* dsm) {
+template <int T, int V, int CIN, int COUT, int EPI, typename Args>
+__device__ __forceinline__ void block_fused_body(const Args& ba, const int n, unsigned char* dsm, const int tid) {
   constexpr int NW = tf_waves<T, V>(), NT = 64 * NW;
   static_assert(!TFusedGeom<T, V, EPI, COUT>::UCH, "pq_sink and tfused_pre write whole E / F rows (UF == T)");
   if constexpr (CIN == 64 && COUT == 64) { TLH(5, 0) }
@@ -2574,8 +2617,9 @@ __device__ __forceinline__ void block_fused_body(const SpatialHLArgs& sa, const 
     // k_adj_hl<0> launch of block 0), stored to HBM like phase 3's and read
     // back by the units below on this CU; every wave's plane stores complete
     // before the barrier (vmcnt 0), the units' loads come after it
+    decltype(auto) s0 = ba.s0();
     if (s0.out) {
-      spatial_adj_sample<T, V, NT, true>(s0, n, dsm);
+      spatial_adj_sample<T, V, NT, true>(s0, n, dsm, tid);
       __builtin_amdgcn_s_waitcnt(0);
       __syncthreads();
     }
@@ -2587,11 +2631,14 @@ __device__ __forceinline__ void block_fused_body(const SpatialHLArgs& sa, const 
     auto& st = *reinterpret_cast<SpatialStage<V, CIN, COUT>*>(dsm);
     static_assert(sizeof(SpatialStage<V, CIN, COUT>) <= TFusedGeom<T, V, EPI, COUT>::PLANES,
                   "the spatial stage must lie within the planes region (tfused_pre writes past it)");
-    stage_spatial<V, CIN, COUT, NT>(sa, st, threadIdx.x);
+    {
+      decltype(auto) sa = ba.s();
+      stage_spatial<V, CIN, COUT, NT>(sa, st, tid);
+    }
     __syncthreads();
-    const int lane = threadIdx.x & 63, kl = lane >> 4, cl = lane & 15;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const SpatialHLArgs& a = sa;
+    const int lane = tid & 63, kl = lane >> 4, cl = lane & 15;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    decltype(auto) a = ba.s();
     constexpr uint32_t adj_bytes = 2 * V * SL * 2;  // one (n, g, t) adjacency: 2 planes of V x SL halves
     const uint32_t wadj0 = kl < NG ? (uint32_t)(cl * SL + 8 * kl) * 2 : OOB;
     auto load_adj_g = [&](int uu, int g, uint4 (&ab)[NWT][2]) {
@@ -2632,23 +2679,120 @@ __device__ __forceinline__ void block_fused_body(const SpatialHLArgs& sa, const 
     // with 8-11 at 2, 8-11 alone: DESIGN.md section 4)
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
     bad = spatial_units<V, CIN, COUT, decltype(load_adj_g), (NW > 8), decltype(pq_sink)>(
-        a, st, n * T + wave, (n + 1) * T, NW, load_adj_g, pq_sink);
+        a, st, tid, n * T + wave, (n + 1) * T, NW, load_adj_g, pq_sink);
     __builtin_amdgcn_s_setprio(0);
   }
   if constexpr (CIN == 64 && COUT == 64) { TLH(5, 1) }
-  tfused_pre<T, V, EPI, COUT>(ta, dsm);
+  {
+    decltype(auto) j = ba.tj();
+    tfused_pre<T, V, EPI, COUT>(j, dsm, tid);
+  }
   // h and the temporal P/Q of sample n written, chunk 0's E / F rows and
   // tables in LDS, the range flags OR-ed; the spatial stage is dead
   const bool sep = __syncthreads_or(bad) == 0;
   if constexpr (CIN == 64 && COUT == 64) { TLH(5, 2) }
-  tfused_body<T, V, EPI, COUT, true>(ta, n, dsm, sep);
+  tfused_body<T, V, EPI, COUT, true>(ba, n, dsm, tid, sep);
   if constexpr (CIN == 64 && COUT == 64) { TLH(5, 3) }
 }
 
 template <int T, int V, int CIN, int COUT, int EPI>
 __global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_waves_per_eu((tf_waves<T, V>() / 4), (tf_waves<T, V>() / 4)))) void k_block_fused(BlockFusedArgs ba) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
-  block_fused_body<T, V, CIN, COUT, EPI>(ba.s, ba.t, ba.s0, blockIdx.x, dsm);  // one sample per workgroup
+  block_fused_body<T, V, CIN, COUT, EPI>(BlockArgsRef{&ba.s, &ba.t, &ba.s0}, blockIdx.x, dsm, threadIdx.x);  // one sample per workgroup
+}
+
+// Block b of a run: each accessor re-reads what its phase needs from the
+// kernel-argument segment through an opaque copy of the segment pointer, so
+// the loads stay in the phase that uses them (as k_block_fused's own argument
+// loads do) -- seen as loop invariants they would be hoisted out of the block
+// loop into SGPRs held through all four phases
+struct EncChainArgsAt {
+  int b;
+  typedef const EncChainArgs __attribute__((address_space(4))) * KP;
+  __device__ __forceinline__ KP base() const {
+    KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();  // EncChainArgs is k_enc_chain's only argument
+    asm volatile("" : "+s"(p));
+    return p;
+  }
+  template <typename S, typename P>
+  __device__ __forceinline__ static S get(P p) {
+    S r;
+    __builtin_memcpy(&r, p, sizeof(S));
+    return r;
+  }
+  __device__ __forceinline__ SpatialHLArgsVal s() const {
+    KP p = base();
+    SpatialHLArgsVal r = get<SpatialHLArgsVal>(&p->s);
+    enc_chain_apply(get<EncChainDesc>(&p->enc[b]), r);
+    return r;
+  }
+  __device__ __forceinline__ TemporalHLArgs tg() const {
+    KP p = base();
+    TemporalHLArgs r = get<TemporalHLArgs>(&p->t.g);
+    enc_chain_apply(get<EncChainDesc>(&p->enc[b]), r);
+    return r;
+  }
+  __device__ __forceinline__ AdjHLArgs tj() const {
+    KP p = base();
+    AdjHLArgs r = get<AdjHLArgs>(&p->t.j);
+    enc_chain_apply_j(get<EncChainDesc>(&p->enc[b]), r);
+    return r;
+  }
+  __device__ __forceinline__ AdjHLArgs tsn() const {
+    KP p = base();
+    AdjHLArgs r = get<AdjHLArgs>(&p->t.sn);
+    enc_chain_apply_sn(get<EncChainDesc>(&p->enc[b]), r);
+    return r;
+  }
+  __device__ __forceinline__ AdjHLArgs s0() const { return AdjHLArgs{}; }  // (conv_st_in only)
+  // (a constant zero vector is hoisted out of the block loop and spilled)
+  __device__ __forceinline__ static uint32_t zero() { return (uint32_t)opaque_zero(); }
+};
+
+// ===========================================================================
+// A run of consecutive encoder blocks in one launch: the workgroup of
+// k_block_fused<64, 64, ENC> runs block_fused_body for block 0, 1, ... of its
+// sample.  Samples are independent in eval, so nothing but the kernel
+// boundary made sample n wait for sample m between blocks; without it the
+// launch's fill / drain and the gap to the next launch are paid once per run,
+// not once per block.  Same unit code in the same order as the per-block
+// launches: bit-identical outputs.
+//
+// The thread, sample and block index reach the body through per-iteration
+// opaque copies.  Seen as loop invariants, every lane-derived address and
+// offset of all four phases is hoisted out of the block loop by LICM and held
+// live through it (107 VGPR spills at H36M); opaque, the body compiles as it
+// does on its own.
+// ===========================================================================
+template <int T, int V>
+__global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_waves_per_eu((tf_waves<T, V>() / 4), (tf_waves<T, V>() / 4)))) void k_enc_chain(EncChainArgs ca) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+#pragma nounroll
+  for (int b = 0; b < ca.nblk; ++b) {
+    int tid = threadIdx.x, n = blockIdx.x, lds0 = 0;
+    asm volatile("" : "+v"(tid));
+    asm volatile("" : "+s"(n), "+s"(lds0));
+    block_fused_body<T, V, 64, 64, TEPI_ENC>(EncChainArgsAt{b}, n, dsm + lds0, tid);
+    // Block boundary.  What a kernel end gave the per-block schedule, the
+    // run provides itself: every wave waits until its own stores (y, the
+    // next block's spatial P/Q and planes) and LDS accesses are complete,
+    // then the workgroup meets.  After the barrier
+    //  * y of block b is complete for every (frame, joint) of the sample: the
+    //    next block's spatial units read it as x, its temporal units as xres;
+    //  * phase 3's planes (adj_s of this sample) are complete: the next
+    //    block's spatial units read them as adj;
+    //  * the temporal units' P/Q (pq_s of this sample) were read by phase 3
+    //    only, the spatial units' P/Q (pq_t) by phase 1 only, and both phases
+    //    are over in every wave: the next block may overwrite them;
+    //  * no wave still reads phase 3's E / F rows, tables and images: the
+    //    next stage_spatial may write LDS from offset 0;
+    //  * s_setprio is 0 (block_fused_body resets it after the spatial units).
+    // All of it is sample n's slice, written and read by this workgroup alone
+    // through the CU's own L1 (workgroup scope, as between the phases of one
+    // block).
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+  }
 }
 
 // ===========================================================================
@@ -2877,6 +3021,94 @@ hipError_t launch_block_fused(const SpatialHLArgs& sa, const TemporalHLArgs& g, 
   if (g.T == 35 && g.V == 22) return bfused_tv<35, 22>(a, s);
   if (g.T == 35 && g.V == 25) return bfused_tv<35, 25>(a, s);
   if (g.T == 40 && g.V == 23) return bfused_tv<40, 23>(a, s);
+  return hipErrorNotSupported;
+}
+
+bool enc_chain_supported(int T, int V) { return block_fused_supported(T, V, 64, 64, TEPI_ENC) && temporal_fused_phase3(T, V); }
+
+hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a) {
+  const SpatialHLArgs& s = a.s;
+  const TemporalHLArgs& g = a.t.g;
+  const AdjHLArgs &j = a.t.j, &n = a.t.sn;
+  if (!enc_chain_supported(g.T, g.V) || s.Cin != 64 || s.Cout != 64 || g.epi != TEPI_ENC || s.xmodel || !n.out ||
+      a.s0.out || g.xres != s.x || s.wimg[2] || s.wscale[2] || s.bf[2] || s.rbn_s || s.rbn_h || j.xin || n.xin)
+    return hipErrorNotSupported;
+  if (c->nblk == 0) {
+    c->s = s;
+    c->t = a.t;
+  } else {
+    // everything outside the descriptor is the run's shared geometry
+    const SpatialHLArgs& s0 = c->s;
+    const TemporalHLArgs& g0 = c->t.g;
+    const AdjHLArgs &j0 = c->t.j, &n0 = c->t.sn;
+    auto same_adj = [](const AdjHLArgs& p, const AdjHLArgs& q) {
+      return p.pq == q.pq && p.pql.sn == q.pql.sn && p.pql.st == q.pql.st && p.pql.sv == q.pql.sv &&
+             p.pql.sch == q.pql.sch && p.p_ch[0] == q.p_ch[0] && p.p_ch[1] == q.p_ch[1] && p.B == q.B &&
+             p.ngroups == q.ngroups && p.out == q.out && p.out_sN == q.out_sN && p.out_sG == q.out_sG &&
+             p.nchunk == q.nchunk;
+    };
+    if (c->nblk >= kEncChainMax || s.B != s0.B || s.T != s0.T || s.V != s0.V || s.adj != s0.adj || s.pq != s0.pq ||
+        g.B != g0.B || g.T != g0.T || g.V != g0.V || g.C != g0.C || g.adj != g0.adj || g.pq != g0.pq ||
+        !same_adj(j, j0) || !same_adj(n, n0))
+      return hipErrorNotSupported;
+  }
+  EncChainDesc& d = c->enc[c->nblk++];
+  d = EncChainDesc{};
+  d.x = s.x;
+  d.h = s.y;
+  for (int i = 0; i < 2; ++i) {
+    d.s_wimg[i] = s.wimg[i];
+    d.s_wscale[i] = s.wscale[i];
+    d.s_bf[i] = s.bf[i];
+    d.s_adjb[i] = s.adjb[i];
+    d.s_pqb[i] = s.pqb[i];
+    d.n_wimg[i] = n.wimg[i];
+    d.n_wscale[i] = n.wscale[i];
+    d.n_bias[i] = n.bias[i];
+    d.n_astat[i] = n.astat[i];
+  }
+  d.s_bn_s = s.bn_s;
+  d.s_bn_h = s.bn_h;
+  d.s_prelu = s.prelu;
+  d.s_pqimg = s.pqimg;
+  d.s_pqscale = s.pqscale;
+  d.t_wimg = g.wimg;
+  d.t_wscale = g.wscale;
+  d.t_bf = g.bf;
+  d.t_adjb = g.adjb;
+  d.t_xres = g.xres;
+  d.t_bn_s = g.bn_s;
+  d.t_bn_h = g.bn_h;
+  d.t_prelu = g.prelu;
+  d.y = g.y;
+  d.t_pqimg = g.pqimg;
+  d.t_pqscale = g.pqscale;
+  for (int i = 0; i < 4; ++i) d.t_pqb[i] = g.pqb[i];
+  d.j_wimg = j.wimg[0];
+  d.j_wscale = j.wscale[0];
+  d.j_bias = j.bias[0];
+  d.j_astat = j.astat[0];
+  d.j_alpha = j.alpha;
+  d.n_alpha = n.alpha;
+  return hipSuccess;
+}
+
+template <int T, int V>
+hipError_t enc_chain_run(const EncChainArgs& c, hipStream_t s) {
+  using Gm = BlockFusedGeom<T, V, 64, 64, TEPI_ENC>;
+  static const hipError_t attr = hipFuncSetAttribute((const void*)k_enc_chain<T, V>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::LDS);
+  if (attr != hipSuccess) return attr;
+  hipLaunchKernelGGL((k_enc_chain<T, V>), dim3(c.t.g.B), dim3(64 * tf_waves<T, V>()), Gm::LDS, s, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_enc_chain(const EncChainArgs& c, hipStream_t s) {
+  if (c.nblk < 1 || c.nblk > kEncChainMax) return hipErrorInvalidValue;
+  const int T = c.t.g.T, V = c.t.g.V;
+  if (T == 35 && V == 22) return enc_chain_run<35, 22>(c, s);
+  if (T == 35 && V == 25) return enc_chain_run<35, 25>(c, s);
+  if (T == 40 && V == 23) return enc_chain_run<40, 23>(c, s);
   return hipErrorNotSupported;
 }
 

@@ -203,6 +203,16 @@ int dstd_model_fwd_profiled(const dstd_model_params* p, const float* x, int B, f
  * and the block is one of the model's three kinds).  Same results bit for
  * bit; for testing and A/B.  Also accepted by dstd_block_fwd_ex. */
 #define DSTD_FWD_SEPARATE_BLOCK 16u
+/* One launch per encoder block.  By default a run of consecutive encoder
+ * blocks that would each be one whole-block launch runs as a single launch
+ * (one workgroup per sample loops over the blocks of the run; up to 8 blocks
+ * per launch): conv_st_in, the encoder run, conv_st_out are 3 launches instead
+ * of num_layers + 2.  Same results bit for bit; for testing and A/B.
+ * DSTD_FWD_SEPARATE_BLOCK and DSTD_FWD_SEPARATE_ADJ imply it.  A call that
+ * carries a profile (prof with capacity > 0) always runs one launch per
+ * block: the event brackets and their block indices are per block.  Accepted
+ * (and without effect) by dstd_block_fwd_ex. */
+#define DSTD_FWD_SEPARATE_ENCODERS 32u
 int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* y, void* workspace,
                       size_t workspace_bytes, void* stream, unsigned flags, dstd_profile* prof);
 int dstd_events_create(int n, void** events);

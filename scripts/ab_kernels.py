@@ -1,12 +1,15 @@
 #!/usr/bin/env python
 """A/B per-kernel-family times of library variants, interleaved in one process.
 
-  python scripts/ab_kernels.py lib1.so lib2.so ... [--rounds 5 --steps 10 --batch 256 --config h36m]
+  python scripts/ab_kernels.py lib1.so lib2.so ... [--rounds 5 --steps 10 --batch 256 --config h36m --json OUT]
 Each library is loaded in turn (ctypes, separate handles) and timed with the
 dstd_model_fwd_profiled event brackets; rounds interleave the variants.
+"wall" is the wall clock of unbracketed forwards (the default schedule: a
+profiled call runs one launch per block).  --json writes every round's values.
 """
 import argparse
 import ctypes
+import json
 import os
 import sys
 import time
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--config", default="h36m")
+    ap.add_argument("--json", default=None, help="write every round's per-family and wall ms per step here")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     model, opts, _ = bench.load_model(a.config, dev)
@@ -72,6 +76,13 @@ def main():
         print(os.path.basename(p), f"wall {np.median(res[p]['wall']):.4f} (min {min(res[p]['wall']):.4f}) "
               f"kernels {tot:.4f} ms/step",
               {k: round(float(np.median(v)), 4) for k, v in res[p].items() if k != "wall"})
+
+
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump({"config": a.config, "batch": a.batch, "rounds": a.rounds, "steps": a.steps,
+                       "ms_per_step": {os.path.basename(p): res[p] for p in a.libs}}, f, indent=1)
+        print("wrote", a.json)
 
 
 if __name__ == "__main__":

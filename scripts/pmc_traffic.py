@@ -20,6 +20,8 @@ from collections import defaultdict
 def family(name):
     # split-f16 kernels (dstd_hilo.hip) are families of their own: the
     # 64->64 launches whose bytes bench.py's roofline divides
+    if "k_enc_chain" in name:  # a run of encoder blocks in one launch (bytes per launch = per run)
+        return "enc_chain_split"
     if "k_block_fused" in name:
         return "block_split"
     if "k_spatial_hl" in name:
