@@ -764,7 +764,9 @@ __global__ __launch_bounds__(256) void k_agg(AggArgs g) {
       int sl[JF];  // LDS slot of (a, i = x*16 + lr) within a channel row
 #pragma unroll
       for (int x = 0; x < JF; ++x) sl[x] = lq(al, x * 16 + lr);
-      for (int c = lk; c < C; c += 4) {
+      // whole groups of 4 channels only (a wave-uniform trip count: every lane
+      // feeds the MFMA); the last C & 3 channels belong to the tail below
+      for (int c = lk; c < (C & ~3); c += 4) {
         float av[JF], bv[JF];
 #pragma unroll
         for (int x = 0; x < JF; ++x) {
