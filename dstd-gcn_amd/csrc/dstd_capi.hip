@@ -8,9 +8,11 @@
 #include <vector>
 
 #include "../../include/dstd_gcn.h"
+#include "../../include/dstd_gcn_taps.h"
 #include "dstd_common.h"
 #include "dstd_hilo.h"
 #include "dstd_kernels.h"
+#include "dstd_taps.h"
 
 using namespace dstd;
 
@@ -263,7 +265,10 @@ struct BlockTail {
 
 // Split-f16 GC kernels (dstd_hilo.hip) where the shape has them, unless the
 // call asks for exact fp32 (DSTD_FWD_EXACT_FP32).
-BlockHL block_hl(const dstd_block_params* p, const BlockTail& tail, int B, int T, int V, unsigned flags) {
+// unit: the unit-parallel schedule at any batch size (the tap entry points:
+// every adjacency in a launch of its own, so that it exists in the scratch).
+BlockHL block_hl(const dstd_block_params* p, const BlockTail& tail, int B, int T, int V, unsigned flags,
+                 bool unit = false) {
   const bool exact = (flags & DSTD_FWD_EXACT_FP32) != 0;
   BlockHL r{false, false, false, false};
   if (exact) return r;
@@ -276,7 +281,7 @@ BlockHL block_hl(const dstd_block_params* p, const BlockTail& tail, int B, int T
   // one workgroup per sample: below one sample per CU the fused kernel leaves
   // CUs idle and the unit-parallel pair (k_adj_hl<1> + k_temporal_hl) wins
   // (B = 16..128: 25-30% faster forward; B = 256: 8% slower, profiles/r03m_small_batch_ab.txt)
-  r.tf = r.t && temporal_fused_supported(T, V) &&
+  r.tf = r.t && !unit && temporal_fused_supported(T, V) &&
          ((B >= hl_device_cus() && temporal_fused_default(T, V)) || (flags & DSTD_FWD_FUSED_TEMPORAL));
   // the whole block as one launch wherever both GCs run split and the
   // temporal one fused (one workgroup per sample either way)
@@ -529,23 +534,49 @@ void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold&
   }
 }
 
+hipError_t to_layout(const float* src, float* dst, int B, int C, int TV, int to_ntvc, hipStream_t s);
+
+// A tapped adjacency (include/dstd_gcn_taps.h) out of the block's scratch,
+// which holds it from the adjacency launch until the next one: split-f16
+// planes decoded ((hi + lo) * 2^sa), fp32 rows compacted.  rows: (sample,
+// graph, frame) spatial, (sample, joint) temporal; NA = V / T.
+hipError_t tap_adjacency(const float* scratch, float* out, bool split, long rows, int NA, int SL, int ld, int seq,
+                         const float* scale0, const float* scale1, hipStream_t s) {
+  if (split) {
+    TapDecodeHLArgs d{reinterpret_cast<const uint16_t*>(scratch), out, rows, NA, SL, seq, {scale0, scale1}};
+    return launch_tap_decode_hl(d, s);
+  }
+  TapCompactArgs c{scratch, out, rows, NA * NA, ld};
+  return launch_tap_compact(c, s);
+}
+
 // One DSTDGCB on NTVC activations.  pq_s must already hold P/Q of x for the
 // block's two spatial DSTDGCs; the block's weight images (add_block_hl_jobs)
 // must be prepared when hl says so.
+// tap (the tap entry points only; needs the unit-parallel schedule, block_hl
+// unit): what to copy out between the launches; x must hold the block's input
+// even where the kernels do not read it (xmodel).
 hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const BlockScratch& sc, int B, int T, int V,
                      const float* x, float* h, float* y, const BlockTail& tail, hipStream_t s, Prof& pf,
-                     const BlockHL& hl, const float* xmodel = nullptr) {
+                     const BlockHL& hl, const float* xmodel = nullptr, const dstd_block_taps* tap = nullptr) {
   BlockArgs A;
   build_block_args(A, p, f, sc, B, T, V, x, h, y, tail, hl, xmodel);
   const bool res = A.res;
+  if (tap && (!A.adj_launch || hl.bf || hl.tf)) return hipErrorInvalidValue;
+  hipError_t e = hipSuccess;
+  if (tap && tap->x) e = to_layout(x, tap->x, B, p->cin, T * V, 0, s);
+  if (e != hipSuccess) return e;
   // (1) spatial adjacency for both graphs
   // (s_pre: already in sc.adj_s, built by the previous block's temporal launch)
-  hipError_t e = hipSuccess;
   if (A.adj_launch) {
     pf.begin(DSTD_KIND_ADJ_S, s);
     e = hl.s ? launch_adj_hl(A.ah, 0, T, V, s) : launch_adj(A.aa, s);
     pf.end(s);
   }
+  if (e != hipSuccess) return e;
+  if (tap && tap->adj_s)
+    e = tap_adjacency(sc.adj_s, tap->adj_s, hl.s, (long)B * 2 * T, V, hl_sl_spatial(V), adj_ld_spatial(V), 0,
+                      hls(f, 5), hls(f, 6), s);
   if (e != hipSuccess) return e;
 
   // (2) spatial GC + bn + residual + prelu, P_t/Q_t of h
@@ -594,6 +625,8 @@ hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const Block
   pf.end(s);
   if (e != hipSuccess) return e;
   }
+  if (tap && tap->h) e = to_layout(h, tap->h, B, p->cout, T * V, 0, s);
+  if (e != hipSuccess) return e;
 
   // (3) temporal adjacency
   if (!hl.tf) {  // the fused temporal kernel builds its adjacency itself
@@ -602,6 +635,10 @@ hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const Block
     pf.end(s);
     if (e != hipSuccess) return e;
   }
+  if (tap && tap->adj_t)
+    e = tap_adjacency(sc.adj_t, tap->adj_t, hl.t, (long)B * V, T, hl_sl_temporal(T), adj_ld_temporal(T), 1, hls(f, 7),
+                      nullptr, s);
+  if (e != hipSuccess) return e;
 
   // (4) temporal GC + tail epilogue (+ next block's spatial P/Q)
   if (hl.t) {
@@ -734,6 +771,12 @@ hipError_t to_layout(const float* src, float* dst, int B, int C, int TV, int to_
   TransposeArgs t{src, dst, B, C, TV, to_ntvc};
   return launch_transpose(t, s);
 }
+
+// the block and the model forward behind the plain and the tap entry points
+int block_fwd(const dstd_block_params* p, const float* x, int B, int T, int V, float* y, void* workspace,
+              size_t workspace_bytes, void* stream, unsigned flags, const dstd_block_taps* taps);
+int model_fwd(const dstd_model_params* p, const float* x, int B, float* y, void* workspace, size_t workspace_bytes,
+              void* stream, unsigned flags, dstd_profile* prof, const dstd_block_taps* taps);
 
 }  // namespace
 
@@ -877,9 +920,31 @@ int dstd_block_fwd(const dstd_block_params* p, const float* x, int B, int T, int
 
 int dstd_block_fwd_ex(const dstd_block_params* p, const float* x, int B, int T, int V, float* y, void* workspace,
                       size_t workspace_bytes, void* stream, unsigned flags) {
-  StreamDeviceGuard dev_guard_(stream, x);
   if (flags & ~(DSTD_FWD_EXACT_FP32 | DSTD_FWD_FUSED_TEMPORAL | DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS))
     return DSTD_EINVAL;
+  return block_fwd(p, x, B, T, V, y, workspace, workspace_bytes, stream, flags, nullptr);
+}
+
+size_t dstd_block_taps_workspace_bytes(int B, int cin, int cout, int T, int V) {
+  return dstd_block_workspace_bytes(B, cin, cout, T, V);
+}
+
+int dstd_block_fwd_taps(const dstd_block_params* p, const float* x, int B, int T, int V, float* y,
+                        const dstd_block_taps* taps, void* workspace, size_t workspace_bytes, void* stream,
+                        unsigned flags) {
+  if ((flags & ~DSTD_FWD_EXACT_FP32) || !taps) return DSTD_EINVAL;
+  return block_fwd(p, x, B, T, V, y, workspace, workspace_bytes, stream, flags, taps);
+}
+
+}  // extern "C"
+
+namespace {
+
+// dstd_block_fwd_ex; taps (dstd_block_fwd_taps): the unit-parallel schedule
+// with the block's taps copied out between its launches
+int block_fwd(const dstd_block_params* p, const float* x, int B, int T, int V, float* y, void* workspace,
+              size_t workspace_bytes, void* stream, unsigned flags, const dstd_block_taps* taps) {
+  StreamDeviceGuard dev_guard_(stream, x);
   if (!x || !y || !workspace || !block_ok(p) || !shape_ok(B, T, V)) return DSTD_EINVAL;
   if (!limits_ok(T, V, p->cin, p->cout)) return DSTD_ELIMIT;
   if (workspace_bytes < dstd_block_workspace_bytes(B, p->cin, p->cout, T, V)) return DSTD_EWORKSPACE;
@@ -893,15 +958,19 @@ int dstd_block_fwd_ex(const dstd_block_params* p, const float* x, int B, int T, 
   DSTD_TRY(to_layout(x, L.xin, B, p->cin, T * V, 1, s));
   DSTD_TRY(spatial_pq(p, L.xin, B, T, V, L.sc.pq_s, s));
   BlockTail tail{TEPI_RAW, nullptr, nullptr, nullptr, nullptr, nullptr};
-  const BlockHL hl = block_hl(p, tail, B, T, V, flags);
+  const BlockHL hl = block_hl(p, tail, B, T, V, flags, taps != nullptr);
   HLList hj;
   add_block_hl_jobs(hj, p, L.f, tail, hl, T, V);
   DSTD_TRY(run_hl_prep(hj, s));
   Prof pf;
-  DSTD_TRY(run_block(p, L.f, L.sc, B, T, V, L.xin, L.h, L.yout, tail, s, pf, hl));
+  DSTD_TRY(run_block(p, L.f, L.sc, B, T, V, L.xin, L.h, L.yout, tail, s, pf, hl, nullptr, taps));
   DSTD_TRY(to_layout(L.yout, y, B, p->cout, T * V, 0, s));
   return DSTD_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int dstd_model_fwd(const dstd_model_params* p, const float* x, int B, float* y, void* workspace,
                    size_t workspace_bytes, void* stream) {
@@ -915,11 +984,34 @@ int dstd_model_fwd_profiled(const dstd_model_params* p, const float* x, int B, f
 
 int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* y, void* workspace,
                       size_t workspace_bytes, void* stream, unsigned flags, dstd_profile* prof) {
-  StreamDeviceGuard dev_guard_(stream, x);
-  const bool reuse = (flags & DSTD_FWD_REUSE_CONSTANTS) != 0;
   if (flags & ~(DSTD_FWD_REUSE_CONSTANTS | DSTD_FWD_EXACT_FP32 | DSTD_FWD_SEPARATE_ADJ | DSTD_FWD_FUSED_TEMPORAL |
                 DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS))
     return DSTD_EINVAL;
+  return model_fwd(p, x, B, y, workspace, workspace_bytes, stream, flags, prof, nullptr);
+}
+
+size_t dstd_model_taps_workspace_bytes(int B, int T, int V, int num_feature, int num_layers) {
+  return dstd_model_workspace_bytes(B, T, V, num_feature, num_layers);
+}
+
+int dstd_model_fwd_taps(const dstd_model_params* p, const float* x, int B, float* y, const dstd_block_taps* taps,
+                        void* workspace, size_t workspace_bytes, void* stream, unsigned flags) {
+  if ((flags & ~DSTD_FWD_EXACT_FP32) || !taps) return DSTD_EINVAL;
+  return model_fwd(p, x, B, y, workspace, workspace_bytes, stream, flags, nullptr, taps);
+}
+
+}  // extern "C"
+
+namespace {
+
+// dstd_model_fwd_ex; taps (dstd_model_fwd_taps, num_layers + 2 entries): the
+// unit-parallel schedule, one launch per adjacency and per GC, with every
+// block's taps copied out between its launches
+int model_fwd(const dstd_model_params* p, const float* x, int B, float* y, void* workspace, size_t workspace_bytes,
+              void* stream, unsigned flags, dstd_profile* prof, const dstd_block_taps* taps) {
+  StreamDeviceGuard dev_guard_(stream, x);
+  if (taps) flags |= DSTD_FWD_SEPARATE_ADJ | DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS;
+  const bool reuse = (flags & DSTD_FWD_REUSE_CONSTANTS) != 0;
   if (!p || !x || !y || !workspace) return DSTD_EINVAL;
   if (prof && (prof->capacity < 0 || (prof->capacity > 0 && (!prof->events || !prof->kinds)))) return DSTD_EINVAL;
   Prof pf;
@@ -997,7 +1089,7 @@ int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* 
   }
   HLList hj;
   for (int b = 0; b < NB; ++b) {
-    hls[b] = block_hl(blk[b], tails[b], B, T, V, flags);
+    hls[b] = block_hl(blk[b], tails[b], B, T, V, flags, taps != nullptr);
     add_block_hl_jobs(hj, blk[b], *fold[b], tails[b], hls[b], T, V);
   }
   // a block's spatial adjacency from the previous block's fused temporal
@@ -1034,7 +1126,9 @@ int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* 
   pa.nw = 4;
   pa.pq = L.sc.pq_s;
   pa.pql = pq_layout_vt(8, T, V);
-  if (!hls[0].s) {  // the split kernels build x6 and these P/Q from x themselves
+  // the split kernels build x6 and these P/Q from x themselves (a tap of
+  // block 0's input still needs x6 in memory)
+  if (!hls[0].s || (taps && taps[0].x)) {
     pf.begin(DSTD_KIND_PREP, s);
     DSTD_TRY(launch_pq(pa, s));
     pf.end(s);
@@ -1069,11 +1163,15 @@ int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* 
     }
     pf.block = b;
     DSTD_TRY(run_block(blk[b], *fold[b], L.sc, B, T, V, xin[b], hbuf[b], ybuf[b], tails[b], s, pf, hls[b],
-                       b == 0 ? x : nullptr));
+                       b == 0 ? x : nullptr, taps ? &taps[b] : nullptr));
     ++b;
   }
   return DSTD_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 
 int dstd_events_create(int n, void** events) {

@@ -52,6 +52,15 @@ class Profile(ctypes.Structure):
                 ("block", ctypes.POINTER(ctypes.c_int)), ("only_block", ctypes.c_int)]
 
 
+class BlockTaps(ctypes.Structure):
+    """include/dstd_gcn_taps.h dstd_block_taps: where one DSTDGCB's taps go
+    (device pointers to dense fp32; None: not wanted, not written)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("adj_s", "adj_t", "x", "h")]
+
+
+TAP_NAMES = ("adj_s", "adj_t", "x", "h")
+
+
 class GCGrads(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("wf", "bf", "wm1", "bm1", "wm2", "bm2", "wrm", "brm")]
 
@@ -253,6 +262,19 @@ def lib():
         L.dstd_conv2d_fwd.argtypes = [vp, ci, ci, ci, ci, vp, vp] + [ci] * 7 + [vp, vp, sz, vp]
         L.dstd_conv2d_bwd.restype = ci
         L.dstd_conv2d_bwd.argtypes = [vp, ci, ci, ci, ci, vp] + [ci] * 7 + [vp, vp, vp, vp, vp, sz, vp]
+        # adjacency / activation taps (include/dstd_gcn_taps.h; absent from
+        # an earlier revision's library loaded for an A/B)
+        if hasattr(L, "dstd_block_fwd_taps"):
+            L.dstd_block_taps_workspace_bytes.restype = sz
+            L.dstd_block_taps_workspace_bytes.argtypes = [ci] * 5
+            L.dstd_model_taps_workspace_bytes.restype = sz
+            L.dstd_model_taps_workspace_bytes.argtypes = [ci] * 5
+            L.dstd_block_fwd_taps.restype = ci
+            L.dstd_block_fwd_taps.argtypes = [ctypes.POINTER(BlockParams), vp, ci, ci, ci, vp,
+                                              ctypes.POINTER(BlockTaps), vp, sz, vp, uf]
+            L.dstd_model_fwd_taps.restype = ci
+            L.dstd_model_fwd_taps.argtypes = [ctypes.POINTER(ModelParams), vp, ci, vp, ctypes.POINTER(BlockTaps), vp,
+                                              sz, vp, uf]
         _lib = L
     return _lib
 
@@ -274,6 +296,8 @@ TRAIN_EXPORTS = ("dstd_dstdgc_train_saved_bytes", "dstd_dstdgc_train_workspace_b
 AUX_EXPORTS = ("dstd_ctg_workspace_bytes", "dstd_ctg_fwd", "dstd_ctg_bwd", "dstd_conv2d_workspace_bytes",
                "dstd_conv2d_fwd", "dstd_conv2d_bwd")
 LOSS_EXPORTS = ("dstd_losses_workspace_bytes", "dstd_losses_fwd", "dstd_losses_bwd")
+TAPS_EXPORTS = ("dstd_block_taps_workspace_bytes", "dstd_model_taps_workspace_bytes", "dstd_block_fwd_taps",
+                "dstd_model_fwd_taps")
 
 
 ARITHMETICS = ("split", "fp32")

@@ -729,6 +729,74 @@ class DSTDGCB(_NativeModule):
         native.check(code, "dstd_block_fwd_ex")
         return y
 
+    def forward_taps(self, x, what=native.TAP_NAMES):
+        """``(y, taps)``: the eval forward of ``x`` [N, cin, T, V] and what it
+        computed on the way (include/dstd_gcn_taps.h) -- ``taps.adj_s``
+        [N, 2, T, V, V] and ``taps.adj_t`` [N, V, T, T], the sample-wise
+        graphs the graph convolutions contracted, ``taps.x`` the block's
+        input and ``taps.h`` [N, cout, T, V] the temporal GC's input.
+        ``what`` names the ones wanted; the others are None.  Eval mode only,
+        no autograd; honours ``gc_arithmetic``.  Runs the unit-parallel launch
+        schedule (one launch per adjacency and per GC); y equals ``self(x)``."""
+        what = _tap_names(what)
+        _taps_eval_only(self)
+        L = native.lib()
+        x = x.detach().contiguous()
+        native.require_device(x, "x")
+        B, cin, T, V = x.shape
+        dev = x.device
+        with torch.no_grad():
+            y = torch.empty(B, self.out_channels, T, V, dtype=torch.float32, device=dev)
+            taps, st = _alloc_taps(what, B, cin, self.out_channels, T, V, dev)
+            if B == 0:
+                return y, taps
+            nbytes = L.dstd_block_taps_workspace_bytes(B, cin, self.out_channels, T, V)
+            ws = native.workspace(dev, nbytes)
+            code = L.dstd_block_fwd_taps(native.block_struct(self), native.ptr(x, "x"), B, T, V, native.ptr(y, "y"),
+                                         st, ws.data_ptr(), ws.numel(), native.stream_handle(dev),
+                                         native.arith_flags(self.gc_arithmetic))
+        native.check(code, "dstd_block_fwd_taps")
+        return y, taps
+
+
+class Taps:
+    """What ``forward_taps`` returns for one DSTDGCB: ``adj_s``, ``adj_t``,
+    ``x``, ``h`` (detached tensors; None where not requested)."""
+    __slots__ = native.TAP_NAMES
+
+    def __init__(self):
+        for n in native.TAP_NAMES:
+            setattr(self, n, None)
+
+    def __repr__(self):
+        return "Taps(" + ", ".join(f"{n}={None if getattr(self, n) is None else list(getattr(self, n).shape)}"
+                                   for n in native.TAP_NAMES) + ")"
+
+
+def _tap_names(what):
+    what = (what,) if isinstance(what, str) else tuple(what)
+    for n in what:
+        if n not in native.TAP_NAMES:
+            raise ValueError(f"forward_taps: unknown tap {n!r} (one of {native.TAP_NAMES})")
+    return what
+
+
+def _taps_eval_only(module):
+    if module.training:
+        raise RuntimeError("forward_taps returns the eval forward's adjacencies and activations: call .eval() first")
+
+
+def _alloc_taps(what, B, cin, cout, T, V, dev):
+    """A Taps with a fresh output tensor per requested name and the C struct
+    that points at them (native.BlockTaps)."""
+    shapes = {"adj_s": (B, 2, T, V, V), "adj_t": (B, V, T, T), "x": (B, cin, T, V), "h": (B, cout, T, V)}
+    taps, st = Taps(), native.BlockTaps()
+    for n in what:
+        t = torch.empty(shapes[n], dtype=torch.float32, device=dev)
+        setattr(taps, n, t)
+        setattr(st, n, t.data_ptr() if t.numel() else None)
+    return taps, st
+
 
 def _ptr_or_none(t):
     return t.data_ptr() if t is not None else None
@@ -994,6 +1062,54 @@ class DSTDGCN(_NativeModule):
         y = torch.empty_like(x)
         self._forward_native(x, y, arith=flags)
         return y
+
+    def forward_taps(self, x, blocks=None, what=native.TAP_NAMES):
+        """``(y, {block index: taps})``: the eval forward of ``x`` [N, T, V, 3]
+        and, per DSTDGCB, the sample-wise graphs and activations it computed
+        (include/dstd_gcn_taps.h; ``DSTDGCB.forward_taps`` describes a block's
+        ``taps``).  Blocks count in forward order: 0 is conv_st_in, 1..L the
+        encoders, L + 1 conv_st_out; ``blocks=None`` taps all of them.  Block
+        0's ``x`` is ``cat(x, x - x[:, -1:])`` as [N, 6, T, V]; an encoder's
+        ``x`` is the previous block's output after its BatchNorm / residual /
+        PReLU.  This is the counterpart of forward hooks on the reference's
+        sub-modules, which cannot fire here (the forward is one native call).
+        Eval mode only, no autograd; honours ``gc_arithmetic``.  Runs the
+        unit-parallel launch schedule at any batch size (one launch per
+        adjacency and per GC) and refolds the constants; y equals ``self(x)``."""
+        what = _tap_names(what)
+        _taps_eval_only(self)
+        n, t, v, c = x.shape
+        assert t == self.input_time_frame + self.output_time_frame
+        if c != self.input_channels // 2 or v != self.joints_to_consider:
+            raise ValueError(f"DSTDGCN: expected [N, {t}, {self.joints_to_consider}, {self.input_channels // 2}], "
+                             f"got {list(x.shape)}")
+        nb = self.num_layers + 2
+        blocks = list(range(nb)) if blocks is None else sorted(set(int(b) for b in blocks))
+        for b in blocks:
+            if not 0 <= b < nb:
+                raise ValueError(f"forward_taps: block {b} outside 0..{nb - 1}")
+        L = native.lib()
+        x = x.detach().contiguous()
+        native.require_device(x, "x")
+        dev = x.device
+        C = self.num_feature
+        with torch.no_grad():
+            y = torch.empty_like(x)
+            out, arr = {}, (native.BlockTaps * nb)()
+            for b in blocks:
+                cin = self.input_channels if b == 0 else C
+                cout = self.input_channels // 2 if b == nb - 1 else C
+                out[b], arr[b] = _alloc_taps(what, n, cin, cout, t, v, dev)
+            if n == 0:
+                return y, out
+            p = self._native_params()
+            nbytes = L.dstd_model_taps_workspace_bytes(n, t, v, C, self.num_layers)
+            # (an untagged claim: the next plain forward folds its constants again)
+            ws = native.workspace(dev, nbytes)
+            code = L.dstd_model_fwd_taps(p, native.ptr(x, "x"), n, native.ptr(y, "y"), arr, ws.data_ptr(), ws.numel(),
+                                         native.stream_handle(dev), native.arith_flags(self.gc_arithmetic))
+        native.check(code, "dstd_model_fwd_taps")
+        return y, out
 
     def forward_pair(self, x1, x2):
         """``(self(x1), self(x2))`` -- PredictionEngine.train's forward of a
