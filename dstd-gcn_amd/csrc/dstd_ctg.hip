@@ -247,8 +247,13 @@ int dstd_conv2d_fwd(const float* x, int B, int cin, int H, int W, const float* w
                     size_t workspace_bytes, void* stream) {
   StreamDeviceGuard dev_guard_(stream, x);
   ConvGeom g;
-  if (!x || !w || !y || !conv_geom(g, B, cin, H, W, cout, kh, kw, sh, sw, ph, pw)) return DSTD_EINVAL;
-  (void)workspace, (void)workspace_bytes;
+  // the forward takes no scratch today; the workspace is checked all the same (non-NULL as in
+  // dstd_conv2d_bwd, then its size), so that every entry point refuses a workspace below its
+  // *_workspace_bytes the same way
+  if (!x || !w || !y || !workspace || !conv_geom(g, B, cin, H, W, cout, kh, kw, sh, sw, ph, pw))
+    return DSTD_EINVAL;
+  if (workspace_bytes < dstd_conv2d_workspace_bytes(B, cin, cout, H, W, kh, kw, sh, sw, ph, pw))
+    return DSTD_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   if (is_pointwise(g)) {
     const long long HW = (long long)H * W;

@@ -21,7 +21,16 @@
  *     device pointers to one float so a call never synchronises.
  *   - Scratch comes from a caller-owned workspace of at least
  *     dstd_*_workspace_bytes(...) bytes; the library allocates nothing and
- *     keeps no state, so calls may be captured into a HIP graph.
+ *     keeps no state, so calls may be captured into a HIP graph.  A call
+ *     reads no byte of the workspace that it has not written itself and
+ *     writes none past the size it asked for; a refused call writes nothing
+ *     (tests/test_gpu_guards.py).
+ *   - The workspace base (and a train forward's `saved` base) must be aligned
+ *     to 256 bytes.  The regions carved from it start at offsets rounded up to
+ *     256 bytes from the base, and kernels address them with 16-byte vector
+ *     loads and stores (the split-f16 weight images are read as uint4), so a
+ *     base of lesser alignment misaligns every region.  This is a requirement
+ *     on the caller; the entry points do not check it.
  *   - Every call is enqueued on `stream` (hipStream_t passed as void*).
  *   - Return 0 on success, a positive hipError_t from a failed launch, or a
  *     negative DSTD_E* code for bad arguments.  dstd_error_string() names it.

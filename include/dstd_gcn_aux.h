@@ -33,7 +33,9 @@ int dstd_ctg_bwd(const float* x, int B, int C, int T, int V, const float* Tm, co
                  void* stream);
 
 /* y [B][cout][Ho][Wo] = conv2d(x [B][cin][H][W], w [cout][cin][kh][kw], bias [cout] or NULL),
- * Ho = (H + 2 ph - kh) / sh + 1, Wo likewise. */
+ * Ho = (H + 2 ph - kh) / sh + 1, Wo likewise.  Forward and backward take the same workspace: a
+ * non-NULL one (else DSTD_EINVAL) of at least dstd_conv2d_workspace_bytes(...) bytes (else
+ * DSTD_EWORKSPACE).  The forward uses no scratch today and is held to that size all the same. */
 size_t dstd_conv2d_workspace_bytes(int B, int cin, int cout, int H, int W, int kh, int kw, int sh, int sw, int ph,
                                    int pw);
 int dstd_conv2d_fwd(const float* x, int B, int cin, int H, int W, const float* w, const float* bias, int cout,
