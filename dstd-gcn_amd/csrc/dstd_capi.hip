@@ -985,7 +985,7 @@ int dstd_model_fwd_profiled(const dstd_model_params* p, const float* x, int B, f
 int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* y, void* workspace,
                       size_t workspace_bytes, void* stream, unsigned flags, dstd_profile* prof) {
   if (flags & ~(DSTD_FWD_REUSE_CONSTANTS | DSTD_FWD_EXACT_FP32 | DSTD_FWD_SEPARATE_ADJ | DSTD_FWD_FUSED_TEMPORAL |
-                DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS))
+                DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS | DSTD_FWD_SEPARATE_ENDS))
     return DSTD_EINVAL;
   return model_fwd(p, x, B, y, workspace, workspace_bytes, stream, flags, prof, nullptr);
 }
@@ -1152,6 +1152,43 @@ int model_fwd(const dstd_model_params* p, const float* x, int B, float* y, void*
     return block_fused_args(A.ha, A.ht, A.aht, &A.sn, &ba, nullptr) == hipSuccess &&
            enc_chain_append(c, ba) == hipSuccess;
   };
+  // The whole forward as one launch (k_model_chain): conv_st_in with its own
+  // planes (adj0), 1..kModelChainMaxEnc encoder blocks that would form one run,
+  // conv_st_out on planes from the last encoder block's phase 3.
+  auto model_chain = [&](ModelChainArgs* c) {
+    if (!chain || (flags & DSTD_FWD_SEPARATE_ENDS) || taps || L_ < 1 || L_ > kModelChainMaxEnc ||
+        !model_chain_supported(T, V) || !hls[0].bf || !hls[0].adj0 || !tails[0].next_adj || !hls[NB - 1].bf ||
+        !hls[NB - 1].s_pre)
+      return false;
+    for (int b = 1; b <= L_; ++b)  // (chain_block's test; model_chain_append validates as enc_chain_append)
+      if (!hls[b].bf || !hls[b].s_pre || !tails[b].next_adj) return false;
+    for (int i = 0; i < NB; ++i) {
+      const int b = i < L_ ? 1 + i : i == L_ ? 0 : NB - 1;  // encoder blocks, conv_st_in, conv_st_out
+      // conv_st_out's h is [B][T][V][3]: in an act buffer, sample n's rows lie
+      // inside the 64-channel slice of sample 3n / 64, which that sample's
+      // workgroup may still be reading or writing as an encoder block's
+      // activation -- between launches every encoder block was over before
+      // conv_st_out began.  Here it goes to the temporal adjacency scratch,
+      // which no launch of this schedule touches (every temporal adjacency is
+      // built in LDS) and which holds B V T T floats or more.
+      float* hb = b == NB - 1 ? L.sc.adj_t : hbuf[b];
+      BlockArgs A;
+      build_block_args(A, blk[b], *fold[b], L.sc, B, T, V, xin[b], hb, ybuf[b], tails[b], hls[b], b == 0 ? x : nullptr);
+      BlockFusedArgs ba;
+      if (block_fused_args(A.ha, A.ht, A.aht, tails[b].next_adj ? &A.sn : nullptr, &ba,
+                           b == 0 && A.from_model ? &A.ah : nullptr) != hipSuccess ||
+          model_chain_append(c, ba) != hipSuccess)
+        return false;
+    }
+    return model_chain_complete(*c);
+  };
+  {
+    ModelChainArgs mc{};
+    if (model_chain(&mc)) {
+      DSTD_TRY(launch_model_chain(mc, s));
+      return DSTD_OK;
+    }
+  }
   for (int b = 0; b < NB;) {
     EncChainArgs c{};
     int e = b;

@@ -497,5 +497,102 @@ bool enc_chain_supported(int T, int V);
 hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a);
 hipError_t launch_enc_chain(const EncChainArgs& c, hipStream_t s);
 
+// ---- the whole eval forward as one launch (k_model_chain) -----------------
+// One workgroup per sample runs conv_st_in (block_fused_body<6, 64, IN>), the
+// encoder blocks and conv_st_out (block_fused_body<64, 3, OUT>) in turn
+// (DESIGN.md section 4, round 8).  The encoder blocks are carried as in
+// EncChainArgs (the first one's arguments as the shared geometry plus a
+// descriptor each); the two end blocks get compact forms over the same
+// geometry -- B, T, V, the P/Q and plane scratch and their layouts are the
+// model's, not a block's -- that carry an encoder descriptor's fields plus what
+// only an end block has.
+struct ModelEndDesc {
+  EncChainDesc e;  // IN: x the model input, t_xres null; OUT: t_xres the model input, no t_pq*, no n_*
+  // the residual conv and its folded BN (Cin != Cout)
+  const uint4* s_wimg2;
+  const float* s_wscale2;
+  const float* s_bf2;
+  const float* s_rbn_s;
+  const float* s_rbn_h;
+};
+// conv_st_in's own spatial planes from the model input (BlockFusedArgs::s0):
+// the shared sn's P/Q layout and output planes with these inputs
+struct ModelAdj0Desc {
+  const float* xin;
+  const float* mw[2][2];
+  const float* mb[2][2];
+  const uint4* wimg[2];
+  const float* wscale[2];
+  const float* bias[2];
+  const float* astat[2];
+  const float* alpha;
+};
+// encoder blocks per launch: what fits 4 KB together with the 256 B of hidden
+// arguments hipcc appends to the segment (longer stacks keep their launches)
+constexpr int kModelChainMaxEnc = 5;
+struct ModelChainArgs {
+  SpatialHLArgs s;      // shared geometry: the first encoder block's arguments
+  TemporalFusedArgs t;
+  int nenc;
+  int have;             // host only: 1 conv_st_in, 2 conv_st_out appended
+  EncChainDesc enc[kModelChainMaxEnc];
+  ModelEndDesc in, out;
+  ModelAdj0Desc in0;
+};
+static_assert(sizeof(ModelChainArgs) + 256 <= 4096, "kernel arguments (with the hidden ones) end at 4 KB");
+__host__ __device__ inline void model_chain_apply_res(const ModelEndDesc& d, SpatialHLArgs& s) {
+  s.wimg[2] = d.s_wimg2;
+  s.wscale[2] = d.s_wscale2;
+  s.bf[2] = d.s_bf2;
+  s.rbn_s = d.s_rbn_s;
+  s.rbn_h = d.s_rbn_h;
+}
+__host__ __device__ inline void model_chain_apply_in(const ModelEndDesc& d, SpatialHLArgs& s) {
+  enc_chain_apply(d.e, s);
+  model_chain_apply_res(d, s);
+  s.xmodel = 1;
+  s.Cin = 6;
+}
+__host__ __device__ inline void model_chain_apply_in(const ModelEndDesc& d, TemporalHLArgs& g) {
+  enc_chain_apply(d.e, g);
+  g.epi = TEPI_IN;
+}
+__host__ __device__ inline void model_chain_apply_in0(const ModelAdj0Desc& d, AdjHLArgs& s0) {
+  s0.xin = d.xin;
+  for (int g = 0; g < 2; ++g) {
+    for (int i = 0; i < 2; ++i) {
+      s0.mw[g][i] = d.mw[g][i];
+      s0.mb[g][i] = d.mb[g][i];
+    }
+    s0.wimg[g] = d.wimg[g];
+    s0.wscale[g] = d.wscale[g];
+    s0.bias[g] = d.bias[g];
+    s0.astat[g] = d.astat[g];
+  }
+  s0.alpha = d.alpha;
+}
+__host__ __device__ inline void model_chain_apply_out(const ModelEndDesc& d, SpatialHLArgs& s) {
+  enc_chain_apply(d.e, s);
+  model_chain_apply_res(d, s);
+  s.Cout = 3;
+}
+__host__ __device__ inline void model_chain_apply_out(const ModelEndDesc& d, TemporalHLArgs& g) {
+  enc_chain_apply(d.e, g);
+  g.C = 3;
+  g.epi = TEPI_OUT;
+  g.pq = nullptr;
+}
+bool model_chain_supported(int T, int V);
+// appends the forward's next block (block_fused_args): the encoder blocks
+// first (1..kModelChainMaxEnc, as enc_chain_append: the first one sets the
+// shared geometry), then conv_st_in (with s0) and conv_st_out in either order.
+// hipErrorNotSupported when the block is none of the three kinds, differs from
+// the shared geometry in anything outside its compact form, or its place is
+// taken: the caller keeps its launches per block / per run
+hipError_t model_chain_append(ModelChainArgs* c, const BlockFusedArgs& a);
+// conv_st_in, at least one encoder block and conv_st_out are in place
+bool model_chain_complete(const ModelChainArgs& c);
+hipError_t launch_model_chain(const ModelChainArgs& c, hipStream_t s);
+
 
 }  // namespace dstd

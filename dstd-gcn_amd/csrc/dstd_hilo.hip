@@ -2795,6 +2795,133 @@ __global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_wave
   }
 }
 
+// Block PH of the whole forward (0 conv_st_in, 1 encoder block b, 2
+// conv_st_out): EncChainArgsAt's accessors over ModelChainArgs, the end blocks
+// through their compact forms.
+template <int PH>
+struct ModelChainArgsAt {
+  int b;
+  typedef const ModelChainArgs __attribute__((address_space(4))) * KP;
+  __device__ __forceinline__ KP base() const {
+    KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();  // ModelChainArgs is k_model_chain's only argument
+    asm volatile("" : "+s"(p));
+    return p;
+  }
+  template <typename S, typename P>
+  __device__ __forceinline__ static S get(P p) {
+    S r;
+    __builtin_memcpy(&r, p, sizeof(S));
+    return r;
+  }
+  __device__ __forceinline__ SpatialHLArgsVal s() const {
+    KP p = base();
+    SpatialHLArgsVal r = get<SpatialHLArgsVal>(&p->s);
+    if constexpr (PH == 0) model_chain_apply_in(get<ModelEndDesc>(&p->in), r);
+    else if constexpr (PH == 1) enc_chain_apply(get<EncChainDesc>(&p->enc[b]), r);
+    else model_chain_apply_out(get<ModelEndDesc>(&p->out), r);
+    return r;
+  }
+  __device__ __forceinline__ TemporalHLArgs tg() const {
+    KP p = base();
+    TemporalHLArgs r = get<TemporalHLArgs>(&p->t.g);
+    if constexpr (PH == 0) model_chain_apply_in(get<ModelEndDesc>(&p->in), r);
+    else if constexpr (PH == 1) enc_chain_apply(get<EncChainDesc>(&p->enc[b]), r);
+    else model_chain_apply_out(get<ModelEndDesc>(&p->out), r);
+    return r;
+  }
+  __device__ __forceinline__ EncChainDesc desc(KP p) const {
+    if constexpr (PH == 0) return get<EncChainDesc>(&p->in.e);
+    else if constexpr (PH == 1) return get<EncChainDesc>(&p->enc[b]);
+    else return get<EncChainDesc>(&p->out.e);
+  }
+  __device__ __forceinline__ AdjHLArgs tj() const {
+    KP p = base();
+    AdjHLArgs r = get<AdjHLArgs>(&p->t.j);
+    enc_chain_apply_j(desc(p), r);
+    return r;
+  }
+  __device__ __forceinline__ AdjHLArgs tsn() const {  // (conv_st_out has no phase 3: C == 3)
+    KP p = base();
+    AdjHLArgs r = get<AdjHLArgs>(&p->t.sn);
+    enc_chain_apply_sn(desc(p), r);
+    return r;
+  }
+  __device__ __forceinline__ AdjHLArgs s0() const {  // conv_st_in: the shared sn's layout and planes, its own inputs
+    if constexpr (PH != 0) return AdjHLArgs{};
+    KP p = base();
+    AdjHLArgs r = get<AdjHLArgs>(&p->t.sn);
+    model_chain_apply_in0(get<ModelAdj0Desc>(&p->in0), r);
+    return r;
+  }
+  __device__ __forceinline__ static uint32_t zero() { return PH == 0 ? 0u : (uint32_t)opaque_zero(); }
+};
+
+// ===========================================================================
+// The whole eval forward in one launch: the workgroup of k_enc_chain runs
+// conv_st_in, the encoder blocks and conv_st_out of its sample, each
+// block_fused_body as it is in its own launch -- the same unit code in the
+// same order, so the output is bit-identical -- with k_enc_chain's block
+// boundary after every block but the last.  The two kernel boundaries that
+// k_enc_chain left inside the forward (fill / drain of a one-wave grid, the
+// gap to the next launch, all CUs forced back into one phase) are gone.
+// The encoder blocks and conv_st_out each get their own opaque copies of the
+// thread, sample and LDS offset (k_enc_chain's reason: invariants of one body
+// hoisted over the others); conv_st_in takes the plain ones (below).
+// ===========================================================================
+template <int T, int V>
+struct ModelChainGeom {
+  static constexpr size_t LI = BlockFusedGeom<T, V, 6, 64, TEPI_IN>::LDS, LE = BlockFusedGeom<T, V, 64, 64, TEPI_ENC>::LDS,
+                          LO = BlockFusedGeom<T, V, 64, 3, TEPI_OUT>::LDS;
+  static constexpr size_t LDS = LI > LE ? (LI > LO ? LI : LO) : (LE > LO ? LE : LO);
+};
+
+#define DSTD_CHAIN_OPAQUE_IDS                      \
+  int tid = threadIdx.x, n = blockIdx.x, lds0 = 0; \
+  asm volatile("" : "+v"(tid));                    \
+  asm volatile("" : "+s"(n), "+s"(lds0));
+// the run's block boundary (k_enc_chain): every wave's stores and LDS accesses
+// complete, then the workgroup meets
+#define DSTD_CHAIN_BOUNDARY          \
+  __builtin_amdgcn_s_waitcnt(0);     \
+  __syncthreads();
+
+template <int T, int V>
+__global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_waves_per_eu((tf_waves<T, V>() / 4), (tf_waves<T, V>() / 4)))) void k_model_chain(ModelChainArgs ca) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
+  {
+    // The launch is one-dimensional, and the kernel says so: __syncthreads_or
+    // forms the flat work-item id ((z dimY + y) dimX + x, dimX from the hidden
+    // arguments), whose pieces are common to all three bodies and were held
+    // in a VGPR and an SGPR from conv_st_in's barrier to conv_st_out's, through
+    // the encoder loop (with the opaque copies: 10 VGPR spills at H36M).
+    // Assumed zero, y and z fold the flat id to threadIdx.x.
+    const unsigned idy = __builtin_amdgcn_workitem_id_y(), idz = __builtin_amdgcn_workitem_id_z();
+    __builtin_assume(idy == 0);
+    __builtin_assume(idz == 0);
+    // conv_st_in takes threadIdx.x, blockIdx.x and the LDS base themselves, as
+    // k_block_fused does: it is at 168 VGPRs on its own and has no room for
+    // an opaque tid beside threadIdx.x, which the later bodies keep live (8
+    // VGPR spills at H36M).  Nothing derived from them can be shared with the
+    // later bodies, whose copies are opaque, and this body is in no loop.
+    block_fused_body<T, V, 6, 64, TEPI_IN>(ModelChainArgsAt<0>{0}, blockIdx.x, dsm, threadIdx.x);
+    // as between encoder blocks (k_enc_chain); conv_st_in's y, temporal P/Q
+    // and phase-3 planes are what the first encoder block reads
+    DSTD_CHAIN_BOUNDARY
+  }
+#pragma nounroll
+  for (int b = 0; b < ca.nenc; ++b) {
+    DSTD_CHAIN_OPAQUE_IDS
+    block_fused_body<T, V, 64, 64, TEPI_ENC>(ModelChainArgsAt<1>{b}, n, dsm + lds0, tid);
+    DSTD_CHAIN_BOUNDARY
+  }
+  {
+    DSTD_CHAIN_OPAQUE_IDS
+    block_fused_body<T, V, 64, 3, TEPI_OUT>(ModelChainArgsAt<2>{0}, n, dsm + lds0, tid);
+  }
+}
+#undef DSTD_CHAIN_OPAQUE_IDS
+#undef DSTD_CHAIN_BOUNDARY
+
 // ===========================================================================
 // dispatch
 // ===========================================================================
@@ -3026,34 +3153,51 @@ hipError_t launch_block_fused(const SpatialHLArgs& sa, const TemporalHLArgs& g, 
 
 bool enc_chain_supported(int T, int V) { return block_fused_supported(T, V, 64, 64, TEPI_ENC) && temporal_fused_phase3(T, V); }
 
-hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a) {
+// a 64 -> 64 ENC block with phase 3, as a run takes it
+static bool enc_chain_kind_ok(const BlockFusedArgs& a) {
   const SpatialHLArgs& s = a.s;
   const TemporalHLArgs& g = a.t.g;
   const AdjHLArgs &j = a.t.j, &n = a.t.sn;
-  if (!enc_chain_supported(g.T, g.V) || s.Cin != 64 || s.Cout != 64 || g.epi != TEPI_ENC || s.xmodel || !n.out ||
-      a.s0.out || g.xres != s.x || s.wimg[2] || s.wscale[2] || s.bf[2] || s.rbn_s || s.rbn_h || j.xin || n.xin)
-    return hipErrorNotSupported;
+  return enc_chain_supported(g.T, g.V) && s.Cin == 64 && s.Cout == 64 && g.epi == TEPI_ENC && !s.xmodel && n.out &&
+         !a.s0.out && g.xres == s.x && !s.wimg[2] && !s.wscale[2] && !s.bf[2] && !s.rbn_s && !s.rbn_h && !j.xin && !n.xin;
+}
+// what an adjacency's arguments share over a run: everything but its weight
+// images, scales, biases, tables and (conv_st_in's s0) model-input fields
+static bool chain_same_adj(const AdjHLArgs& p, const AdjHLArgs& q) {
+  return p.pq == q.pq && p.pql.sn == q.pql.sn && p.pql.st == q.pql.st && p.pql.sv == q.pql.sv &&
+         p.pql.sch == q.pql.sch && p.p_ch[0] == q.p_ch[0] && p.p_ch[1] == q.p_ch[1] && p.B == q.B &&
+         p.ngroups == q.ngroups && p.out == q.out && p.out_sN == q.out_sN && p.out_sG == q.out_sG &&
+         p.nchunk == q.nchunk;
+}
+// an encoder block's arguments outside its descriptor equal the shared geometry (s0, t0)
+static bool enc_chain_same_geometry(const BlockFusedArgs& a, const SpatialHLArgs& s0, const TemporalFusedArgs& t0) {
+  const SpatialHLArgs& s = a.s;
+  const TemporalHLArgs &g = a.t.g, &g0 = t0.g;
+  return s.B == s0.B && s.T == s0.T && s.V == s0.V && s.adj == s0.adj && s.pq == s0.pq && g.B == g0.B && g.T == g0.T &&
+         g.V == g0.V && g.C == g0.C && g.adj == g0.adj && g.pq == g0.pq && chain_same_adj(a.t.j, t0.j) &&
+         chain_same_adj(a.t.sn, t0.sn);
+}
+static EncChainDesc enc_chain_desc(const BlockFusedArgs& a);
+
+hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a) {
+  if (!enc_chain_kind_ok(a)) return hipErrorNotSupported;
   if (c->nblk == 0) {
-    c->s = s;
+    c->s = a.s;
     c->t = a.t;
-  } else {
-    // everything outside the descriptor is the run's shared geometry
-    const SpatialHLArgs& s0 = c->s;
-    const TemporalHLArgs& g0 = c->t.g;
-    const AdjHLArgs &j0 = c->t.j, &n0 = c->t.sn;
-    auto same_adj = [](const AdjHLArgs& p, const AdjHLArgs& q) {
-      return p.pq == q.pq && p.pql.sn == q.pql.sn && p.pql.st == q.pql.st && p.pql.sv == q.pql.sv &&
-             p.pql.sch == q.pql.sch && p.p_ch[0] == q.p_ch[0] && p.p_ch[1] == q.p_ch[1] && p.B == q.B &&
-             p.ngroups == q.ngroups && p.out == q.out && p.out_sN == q.out_sN && p.out_sG == q.out_sG &&
-             p.nchunk == q.nchunk;
-    };
-    if (c->nblk >= kEncChainMax || s.B != s0.B || s.T != s0.T || s.V != s0.V || s.adj != s0.adj || s.pq != s0.pq ||
-        g.B != g0.B || g.T != g0.T || g.V != g0.V || g.C != g0.C || g.adj != g0.adj || g.pq != g0.pq ||
-        !same_adj(j, j0) || !same_adj(n, n0))
-      return hipErrorNotSupported;
+  } else if (c->nblk >= kEncChainMax || !enc_chain_same_geometry(a, c->s, c->t)) {
+    return hipErrorNotSupported;
   }
-  EncChainDesc& d = c->enc[c->nblk++];
-  d = EncChainDesc{};
+  c->enc[c->nblk++] = enc_chain_desc(a);
+  return hipSuccess;
+}
+
+// the descriptor fields of a block's arguments (for conv_st_out, which has no
+// phase 3 and no P/Q conv, those stay null)
+static EncChainDesc enc_chain_desc(const BlockFusedArgs& a) {
+  const SpatialHLArgs& s = a.s;
+  const TemporalHLArgs& g = a.t.g;
+  const AdjHLArgs &j = a.t.j, &n = a.t.sn;
+  EncChainDesc d{};
   d.x = s.x;
   d.h = s.y;
   for (int i = 0; i < 2; ++i) {
@@ -3090,7 +3234,7 @@ hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a) {
   d.j_astat = j.astat[0];
   d.j_alpha = j.alpha;
   d.n_alpha = n.alpha;
-  return hipSuccess;
+  return d;
 }
 
 template <int T, int V>
@@ -3109,6 +3253,97 @@ hipError_t launch_enc_chain(const EncChainArgs& c, hipStream_t s) {
   if (T == 35 && V == 22) return enc_chain_run<35, 22>(c, s);
   if (T == 35 && V == 25) return enc_chain_run<35, 25>(c, s);
   if (T == 40 && V == 23) return enc_chain_run<40, 23>(c, s);
+  return hipErrorNotSupported;
+}
+
+bool model_chain_supported(int T, int V) {
+  return enc_chain_supported(T, V) && block_fused_adj0_supported(T, V) && block_fused_supported(T, V, 64, 3, TEPI_OUT);
+}
+
+bool model_chain_complete(const ModelChainArgs& c) { return c.nenc >= 1 && c.have == 3; }
+
+hipError_t model_chain_append(ModelChainArgs* c, const BlockFusedArgs& a) {
+  const SpatialHLArgs& s = a.s;
+  const TemporalHLArgs& g = a.t.g;
+  const AdjHLArgs &j = a.t.j, &n = a.t.sn;
+  if (!model_chain_supported(g.T, g.V)) return hipErrorNotSupported;
+  const bool enc = s.Cin == 64 && s.Cout == 64 && g.epi == TEPI_ENC;
+  const bool in = s.Cin == 6 && s.Cout == 64 && g.epi == TEPI_IN, out = s.Cin == 64 && s.Cout == 3 && g.epi == TEPI_OUT;
+  if (enc) {
+    // the encoder blocks exactly as a run of k_enc_chain takes them
+    if (c->have || c->nenc >= kModelChainMaxEnc || !enc_chain_kind_ok(a)) return hipErrorNotSupported;
+    if (c->nenc == 0) {
+      c->s = s;
+      c->t = a.t;
+    } else if (!enc_chain_same_geometry(a, c->s, c->t)) {
+      return hipErrorNotSupported;
+    }
+    c->enc[c->nenc++] = enc_chain_desc(a);
+    return hipSuccess;
+  }
+  if (!(in || out) || c->nenc < 1 || (c->have & (in ? 1 : 2))) return hipErrorNotSupported;
+  // everything outside the compact form is the shared geometry
+  const SpatialHLArgs& sg = c->s;
+  const TemporalHLArgs& gg = c->t.g;
+  const AdjHLArgs &jg = c->t.j, &ng = c->t.sn;
+  if (s.B != sg.B || s.T != sg.T || s.V != sg.V || s.adj != sg.adj || s.pq != sg.pq || g.B != gg.B || g.T != gg.T ||
+      g.V != gg.V || g.adj != gg.adj || !chain_same_adj(j, jg) || j.xin || !s.wimg[2] || !s.wscale[2] || !s.bf[2] ||
+      !s.rbn_s || !s.rbn_h)
+    return hipErrorNotSupported;
+  if (in) {
+    const AdjHLArgs& z = a.s0;
+    if (!s.xmodel || g.C != gg.C || g.pq != gg.pq || g.xres || !n.out || n.xin || !chain_same_adj(n, ng) || !z.out ||
+        z.xin != s.x || !chain_same_adj(z, ng))
+      return hipErrorNotSupported;
+  } else {
+    if (s.xmodel || g.C != 3 || g.pq || g.pqimg || g.pqscale || n.out || a.s0.out || !g.xres)
+      return hipErrorNotSupported;
+  }
+  ModelEndDesc& d = in ? c->in : c->out;
+  d = ModelEndDesc{};
+  d.e = enc_chain_desc(a);
+  d.s_wimg2 = s.wimg[2];
+  d.s_wscale2 = s.wscale[2];
+  d.s_bf2 = s.bf[2];
+  d.s_rbn_s = s.rbn_s;
+  d.s_rbn_h = s.rbn_h;
+  if (in) {
+    const AdjHLArgs& z = a.s0;
+    ModelAdj0Desc& q = c->in0;
+    q = ModelAdj0Desc{};
+    q.xin = z.xin;
+    for (int i = 0; i < 2; ++i) {
+      for (int k = 0; k < 2; ++k) {
+        q.mw[i][k] = z.mw[i][k];
+        q.mb[i][k] = z.mb[i][k];
+      }
+      q.wimg[i] = z.wimg[i];
+      q.wscale[i] = z.wscale[i];
+      q.bias[i] = z.bias[i];
+      q.astat[i] = z.astat[i];
+    }
+    q.alpha = z.alpha;
+  }
+  c->have |= in ? 1 : 2;
+  return hipSuccess;
+}
+
+template <int T, int V>
+hipError_t model_chain_run(const ModelChainArgs& c, hipStream_t s) {
+  using Gm = ModelChainGeom<T, V>;
+  static const hipError_t attr = hipFuncSetAttribute((const void*)k_model_chain<T, V>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::LDS);
+  if (attr != hipSuccess) return attr;
+  hipLaunchKernelGGL((k_model_chain<T, V>), dim3(c.t.g.B), dim3(64 * tf_waves<T, V>()), Gm::LDS, s, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_model_chain(const ModelChainArgs& c, hipStream_t s) {
+  if (!model_chain_complete(c) || c.nenc > kModelChainMaxEnc) return hipErrorInvalidValue;
+  const int T = c.t.g.T, V = c.t.g.V;
+  if (T == 35 && V == 22) return model_chain_run<35, 22>(c, s);
+  if (T == 35 && V == 25) return model_chain_run<35, 25>(c, s);
+  if (T == 40 && V == 23) return model_chain_run<40, 23>(c, s);
   return hipErrorNotSupported;
 }
 

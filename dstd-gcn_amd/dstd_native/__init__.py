@@ -114,6 +114,7 @@ FWD_SEPARATE_ADJ = 4  # include/dstd_gcn.h DSTD_FWD_SEPARATE_ADJ
 FWD_FUSED_TEMPORAL = 8  # include/dstd_gcn.h DSTD_FWD_FUSED_TEMPORAL
 FWD_SEPARATE_BLOCK = 16  # include/dstd_gcn.h DSTD_FWD_SEPARATE_BLOCK
 FWD_SEPARATE_ENCODERS = 32  # include/dstd_gcn.h DSTD_FWD_SEPARATE_ENCODERS
+FWD_SEPARATE_ENDS = 64  # include/dstd_gcn.h DSTD_FWD_SEPARATE_ENDS
 KIND_FOLD, KIND_PREP, KIND_ADJ_S, KIND_SPATIAL, KIND_ADJ_T, KIND_TEMPORAL, KIND_BLOCK = range(7)
 KIND_NAMES = ("fold", "prep", "adj_spatial", "spatial_gc", "adj_temporal", "temporal_gc", "block")
 

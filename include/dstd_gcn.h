@@ -222,6 +222,15 @@ int dstd_model_fwd_profiled(const dstd_model_params* p, const float* x, int B, f
  * block: the event brackets and their block indices are per block.  Accepted
  * (and without effect) by dstd_block_fwd_ex. */
 #define DSTD_FWD_SEPARATE_ENCODERS 32u
+/* conv_st_in and conv_st_out in launches of their own around the encoder
+ * run (3 launches per forward).  By default the whole forward -- conv_st_in,
+ * 1 to 5 encoder blocks, conv_st_out -- is one launch where every block would
+ * be a whole-block launch (one workgroup per sample runs the sample's blocks
+ * in turn); num_layers 0 or above 5 keeps the 3-launch schedule.  Same
+ * results bit for bit; for testing and A/B.  DSTD_FWD_SEPARATE_ENCODERS,
+ * DSTD_FWD_SEPARATE_BLOCK and DSTD_FWD_SEPARATE_ADJ imply it, and so does a
+ * call that carries a profile.  dstd_model_fwd_ex only. */
+#define DSTD_FWD_SEPARATE_ENDS 64u
 int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* y, void* workspace,
                       size_t workspace_bytes, void* stream, unsigned flags, dstd_profile* prof);
 int dstd_events_create(int n, void** events);

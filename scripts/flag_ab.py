@@ -3,7 +3,8 @@
 own eval forward (_forward_native, constants reused) timed per flag set.
 
   python scripts/flag_ab.py [--config h36m] [--rounds 5] [--steps 50] [--batch 256] name=flags ...
-e.g. default=0 whole=32 (include/dstd_gcn.h DSTD_FWD_*)."""
+e.g. default=0 ends=64 encoders=32 (include/dstd_gcn.h DSTD_FWD_*: one launch per
+forward, conv_st_in / encoder run / conv_st_out, one launch per block)."""
 import argparse
 import os
 import sys
