@@ -12,6 +12,7 @@
 #include "dstd_common.h"
 #include "dstd_hilo.h"
 #include "dstd_kernels.h"
+#include "dstd_plan.h"
 #include "dstd_taps.h"
 
 using namespace dstd;
@@ -45,6 +46,14 @@ bool shape_ok(int B, int T, int V) { return B > 0 && T > 1 && V > 0; }
 bool limits_ok(int T, int V, int cin, int cout) {
   return T <= kMaxT && V <= kMaxV && cin >= 1 && cin <= kMaxC && cout >= 1 && cout <= kMaxC;
 }
+// the model's integer arguments (dstd_model_fwd_ex and dstd_model_fwd_schedule alike)
+int model_shape_code(int B, int T, int V, int C, int layers) {
+  if (!shape_ok(B, T, V) || layers < 0 || layers > DSTD_MAX_LAYERS) return DSTD_EINVAL;
+  return limits_ok(T, V, 6, C) ? DSTD_OK : DSTD_ELIMIT;
+}
+constexpr unsigned kModelFwdFlags = DSTD_FWD_REUSE_CONSTANTS | DSTD_FWD_EXACT_FP32 | DSTD_FWD_SEPARATE_ADJ |
+                                    DSTD_FWD_FUSED_TEMPORAL | DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS |
+                                    DSTD_FWD_SEPARATE_ENDS;
 bool gc_ok(const dstd_gc_weights* w) {
   return w && w->wf && w->bf && w->wm1 && w->bm1 && w->wm2 && w->bm2 && w->wrm && w->brm;
 }
@@ -94,15 +103,6 @@ struct BlockFold {
   uint4* hl_rmt;    // conv_t.conv_rm (temporal adjacency)
   float* hl_scale;  // 9 scale slots (kHLSlot floats each, dstd_hilo.h): ws0, ws1, pqs, wt, pqt, rms0, rms1, rmt, ws2
   float* hl_rbias;  // [2T + V]: fused conv_rm biases (HLJob::bias_out) of rms0, rms1, rmt
-};
-
-// Which GC launches of a block run the split-f16 kernels; tf: the temporal
-// one with its adjacency built in LDS (k_temporal_fused, no k_adj_hl<1>).
-struct BlockHL {
-  bool s, t, tf;
-  bool s_pre = false;  // the spatial adjacency planes were built by the previous block's temporal launch
-  bool bf = false;     // spatial + fused temporal GC in one launch (k_block_fused)
-  bool adj0 = false;   // (conv_st_in with bf) its spatial planes from the model input in that launch
 };
 
 struct BlockScratch {
@@ -258,35 +258,46 @@ struct BlockTail {
   const float* bn_h;
   const float* prelu;
   const dstd_block_params* next;  // next block: its spatial P/Q are produced here
-  // the next block's spatial adjacency planes are built here too (k_temporal_fused phase 3)
+  // its folded constants: its spatial adjacency planes are built here too
+  // where the plan says so (BlockPlan::next_adj, k_temporal_fused phase 3)
   const BlockFold* next_f = nullptr;
-  bool next_adj = false;
 };
 
-// Split-f16 GC kernels (dstd_hilo.hip) where the shape has them, unless the
-// call asks for exact fp32 (DSTD_FWD_EXACT_FP32).
-// unit: the unit-parallel schedule at any batch size (the tap entry points:
-// every adjacency in a launch of its own, so that it exists in the scratch).
-BlockHL block_hl(const dstd_block_params* p, const BlockTail& tail, int B, int T, int V, unsigned flags,
-                 bool unit = false) {
-  const bool exact = (flags & DSTD_FWD_EXACT_FP32) != 0;
-  BlockHL r{false, false, false, false};
-  if (exact) return r;
-  r.s = spatial_hl_supported(T, V) &&
-        ((p->cin == 64 && p->cout == 64) || (p->cin == 6 && p->cout == 64) || (p->cin == 64 && p->cout == 3));
-  r.t = temporal_hl_supported(T, V) &&
-        ((p->cout == 64 && (tail.epi == TEPI_ENC || tail.epi == TEPI_IN || tail.epi == TEPI_RAW) &&
-          (!tail.next || tail.next->cin == 64)) ||
-         (p->cout == 3 && (tail.epi == TEPI_OUT || tail.epi == TEPI_RAW) && !tail.next));
-  // one workgroup per sample: below one sample per CU the fused kernel leaves
-  // CUs idle and the unit-parallel pair (k_adj_hl<1> + k_temporal_hl) wins
-  // (B = 16..128: 25-30% faster forward; B = 256: 8% slower, profiles/r03m_small_batch_ab.txt)
-  r.tf = r.t && !unit && temporal_fused_supported(T, V) &&
-         ((B >= hl_device_cus() && temporal_fused_default(T, V)) || (flags & DSTD_FWD_FUSED_TEMPORAL));
-  // the whole block as one launch wherever both GCs run split and the
-  // temporal one fused (one workgroup per sample either way)
-  r.bf = r.s && r.tf && !(flags & DSTD_FWD_SEPARATE_BLOCK) && block_fused_supported(T, V, p->cin, p->cout, tail.epi);
-  return r;
+// One DSTDGCB of a forward: parameters, folded constants, NTVC buffers
+// (x -> spatial GC -> h -> temporal GC + tail -> y).
+struct BlockRun {
+  const dstd_block_params* p;
+  const BlockFold* f;
+  const float* x;
+  float* h;
+  float* y;
+  BlockTail tail;
+};
+
+// conv_m1 / conv_m2 of a block's two spatial DSTDGCs: the four two-row weight
+// blocks and biases behind its spatial P/Q (channels P_0, Q_0, P_1, Q_1 pairs)
+struct SpatialPQ {
+  const float* w[4];
+  const float* b[4];
+};
+SpatialPQ spatial_pq_params(const dstd_block_params* p) {
+  const dstd_gc_weights &g0 = p->conv_s[0], &g1 = p->conv_s[1];
+  return SpatialPQ{{g0.wm1, g0.wm2, g1.wm1, g1.wm2}, {g0.bm1, g0.bm2, g1.bm1, g1.bm2}};
+}
+
+// The generic (fp32 rows) adjacency geometry of a mode, one graph per sample:
+// nrow, K, NA, ncol, ldo, out_sN.
+void adj_geometry(AdjArgs& a, int mode, int T, int V) {
+  const bool sp = mode == DSTD_MODE_SPATIAL;
+  a.mode = mode;
+  a.T = T;
+  a.V = V;
+  a.nrow = sp ? T : V;
+  a.K = 2 * a.nrow;
+  a.NA = sp ? V : T;
+  a.ncol = a.NA * a.NA;
+  a.ldo = sp ? adj_ld_spatial(V) : adj_ld_temporal(T);
+  a.out_sN = (long)a.nrow * a.ldo;
 }
 
 // scale slot i of a block's weight images (BlockFold::hl_scale)
@@ -294,7 +305,7 @@ float* hls(const BlockFold& f, int i) { return f.hl_scale + kHLSlot * i; }
 
 // Weight images of the block's split-f16 launches.
 void add_block_hl_jobs(HLList& l, const dstd_block_params* p, const BlockFold& f, const BlockTail& tail,
-                       const BlockHL& hl, int T, int V) {
+                       const BlockPlan& hl, int T, int V) {
   if (hl.s) {
     add_hl_rm(l, p->conv_s[0].wrm, p->conv_s[0].brm, T, 2 * T, f.hl_rms[0], hls(f, 5), f.hl_rbias, p->alpha_sm,
               f.astat_s, V * V);
@@ -310,37 +321,41 @@ void add_block_hl_jobs(HLList& l, const dstd_block_params* p, const BlockFold& f
     add_hl_rm(l, p->conv_t.wrm, p->conv_t.brm, V, 2 * V, f.hl_rmt, hls(f, 7), f.hl_rbias + 2 * T, p->alpha_tm,
               f.astat_t, T * T);
     add_hl_conv(l, p->conv_t.wf, p->conv_t.bf, p->cout, p->cout, f.hl_wt, hls(f, 3));
-    if (tail.next) {
-      const dstd_block_params* q = tail.next;
-      const float* w[4] = {q->conv_s[0].wm1, q->conv_s[0].wm2, q->conv_s[1].wm1, q->conv_s[1].wm2};
-      add_hl_pq(l, w, 4, 64, f.hl_pqt, hls(f, 4));
-    }
+    if (tail.next) add_hl_pq(l, spatial_pq_params(tail.next).w, 4, 64, f.hl_pqt, hls(f, 4));
   }
 }
 
-// The arguments of one DSTDGCB's launches on NTVC activations (run_block
-// launches them one block at a time, the encoder chain packs a run of them
-// into one launch): aa / ta the adjacency launches, and where hl says so
-// their split-f16 forms ah / aht, the split GC kernels ha / ht and the next
-// block's spatial adjacency sn (tail.next_adj).
+// The arguments of every launch a DSTDGCB can take part in, on NTVC
+// activations, built once per block whatever the plan does with it (its own
+// launches, a run of k_enc_chain, k_model_chain): aa / ta the adjacency
+// launches and sa / tt the GC launches of the generic fp32 kernels; where hl
+// says so the split-f16 forms instead: ah / aht, the GC kernels ha / ht and
+// the next block's spatial adjacency sn (hl.next_adj).
 // xmodel (conv_st_in of the model, split spatial only): the model input
 // [B][T][V][3]; the kernels build x6 and block-0's spatial P/Q from it, x is
 // not read.
 struct BlockArgs {
-  bool res, from_model, adj_launch;
+  bool from_model;
   AdjArgs aa, ta;
+  SpatialArgs sa;
+  TemporalArgs tt;
   AdjHLArgs ah, aht, sn;
   SpatialHLArgs ha;
   TemporalHLArgs ht;
 };
-void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold& f, const BlockScratch& sc, int B, int T,
-                      int V, const float* x, float* h, float* y, const BlockTail& tail, const BlockHL& hl,
+void build_block_args(BlockArgs& A, const BlockRun& r, const BlockScratch& sc, int B, int T, int V, const BlockPlan& hl,
                       const float* xmodel) {
   A = BlockArgs{};
-  const bool res = A.res = p->cin != p->cout;
+  const dstd_block_params* p = r.p;
+  const BlockFold& f = *r.f;
+  const BlockTail& tail = r.tail;
+  const float* x = r.x;
+  float *h = r.h, *y = r.y;
+  const bool res = p->cin != p->cout;
   const bool from_model = A.from_model = xmodel && hl.s && p->cin == 6;
-  A.adj_launch = !hl.s_pre && !(hl.adj0 && from_model);
   AdjArgs &aa = A.aa, &ta = A.ta;
+  SpatialArgs& sa = A.sa;
+  TemporalArgs& tt = A.tt;
   AdjHLArgs &ah = A.ah, &aht = A.aht, &sn = A.sn;
   SpatialHLArgs& ha = A.ha;
   TemporalHLArgs& ht = A.ht;
@@ -354,14 +369,8 @@ void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold&
     aa.bias[g] = p->conv_s[g].brm;
     aa.astat[g] = f.astat_s + g * V * V;
   }
-  aa.mode = 0;
+  adj_geometry(aa, DSTD_MODE_SPATIAL, T, V);
   aa.B = B;
-  aa.T = T;
-  aa.V = V;
-  aa.nrow = T;
-  aa.K = 2 * T;
-  aa.NA = V;
-  aa.ncol = V * V;
   aa.ngroups = 2;
   aa.alpha = p->alpha_sm;
   aa.out = sc.adj_s;
@@ -369,13 +378,10 @@ void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold&
     aa.hl = 1;
     aa.ncol = V * hl_sl_spatial(V);
     aa.ldo = 2 * aa.ncol;
-    aa.out_sG = (long)T * aa.ncol;
-    aa.out_sN = 2 * aa.out_sG;
-  } else {
-    aa.ldo = adj_ld_spatial(V);
-    aa.out_sN = 2L * T * aa.ldo;
-    aa.out_sG = (long)T * aa.ldo;
+    aa.out_sN = (long)T * aa.ncol;
   }
+  aa.out_sG = aa.out_sN;  // [B][2 graphs]
+  aa.out_sN = 2 * aa.out_sG;
   if (hl.s) {
     ah.pq = aa.pq;
     ah.pql = aa.pql;
@@ -394,11 +400,10 @@ void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold&
     ah.out_sG = 2 * aa.out_sG;
     if (from_model) {
       ah.xin = xmodel;
-      for (int g = 0; g < 2; ++g) {
-        ah.mw[g][0] = p->conv_s[g].wm1;
-        ah.mw[g][1] = p->conv_s[g].wm2;
-        ah.mb[g][0] = p->conv_s[g].bm1;
-        ah.mb[g][1] = p->conv_s[g].bm2;
+      const SpatialPQ m = spatial_pq_params(p);
+      for (int i = 0; i < 4; ++i) {
+        ah.mw[i / 2][i % 2] = m.w[i];
+        ah.mb[i / 2][i % 2] = m.b[i];
       }
     }
   }
@@ -435,6 +440,38 @@ void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold&
     ha.pqb[0] = p->conv_t.bm1;
     ha.pqb[1] = p->conv_t.bm2;
     ha.pq = sc.pq_t;
+  } else {
+    sa.x = x;
+    sa.B = B;
+    sa.T = T;
+    sa.V = V;
+    sa.Cin = p->cin;
+    sa.Cout = p->cout;
+    sa.NI = 2;
+    sa.G = res ? 3 : 2;
+    sa.adj = sc.adj_s;
+    sa.adj_ld = adj_ld_spatial(V);
+    for (int g = 0; g < 2; ++g) {
+      sa.wf[g] = p->conv_s[g].wf;
+      sa.bf[g] = p->conv_s[g].bf;
+    }
+    sa.wf[2] = res ? p->res_w : nullptr;
+    sa.bf[2] = res ? p->res_b : nullptr;
+    sa.epi = 1;
+    sa.bn_s = f.bn_s;
+    sa.bn_h = f.bn_h;
+    sa.rbn_s = f.rbn_s;
+    sa.rbn_h = f.rbn_h;
+    sa.prelu = p->prelu;
+    sa.y = h;
+    sa.pqw[0] = p->conv_t.wm1;
+    sa.pqw[1] = p->conv_t.wm2;
+    sa.pqb[0] = p->conv_t.bm1;
+    sa.pqb[1] = p->conv_t.bm2;
+    sa.npqw = 2;
+    sa.pq = sc.pq_t;
+    sa.pql = pq_layout_tv(4, T, V);
+    sa.Tt = 0;
   }
 
   // (3) temporal adjacency
@@ -445,14 +482,8 @@ void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold&
   ta.W[0] = p->conv_t.wrm;
   ta.bias[0] = p->conv_t.brm;
   ta.astat[0] = f.astat_t;
-  ta.mode = 1;
+  adj_geometry(ta, DSTD_MODE_TEMPORAL, T, V);
   ta.B = B;
-  ta.T = T;
-  ta.V = V;
-  ta.nrow = V;
-  ta.K = 2 * V;
-  ta.NA = T;
-  ta.ncol = T * T;
   ta.ngroups = 1;
   ta.alpha = p->alpha_tm;
   ta.out = sc.adj_t;
@@ -462,9 +493,6 @@ void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold&
     ta.ncol = T * hl_sl_temporal(T);
     ta.ldo = 2 * ta.ncol;
     ta.out_sN = (long)V * ta.ncol;
-  } else {
-    ta.ldo = adj_ld_temporal(T);
-    ta.out_sN = (long)V * ta.ldo;
   }
   if (hl.t) {
     aht.pq = ta.pq;
@@ -501,17 +529,14 @@ void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold&
     ht.prelu = tail.prelu;
     ht.y = y;
     if (tail.next) {
-      const dstd_block_params* q = tail.next;
+      const SpatialPQ m = spatial_pq_params(tail.next);
       ht.pqimg = f.hl_pqt;
       ht.pqscale = hls(f, 4);
-      ht.pqb[0] = q->conv_s[0].bm1;
-      ht.pqb[1] = q->conv_s[0].bm2;
-      ht.pqb[2] = q->conv_s[1].bm1;
-      ht.pqb[3] = q->conv_s[1].bm2;
+      for (int i = 0; i < 4; ++i) ht.pqb[i] = m.b[i];
       ht.pq = sc.pq_s;
     }
     // the next block's spatial adjacency (its launch_adj_hl mode 0 arguments)
-    if (tail.next_adj) {
+    if (hl.next_adj) {
       const dstd_block_params* q = tail.next;
       const BlockFold& nf = *tail.next_f;
       const int ncol = V * hl_sl_spatial(V);
@@ -531,6 +556,34 @@ void build_block_args(BlockArgs& A, const dstd_block_params* p, const BlockFold&
       sn.out_sG = 2L * T * ncol;  // halves
       sn.out_sN = 2 * sn.out_sG;
     }
+  } else {
+    tt.h = h;
+    tt.B = B;
+    tt.T = T;
+    tt.V = V;
+    tt.Cin = p->cout;
+    tt.Cout = p->cout;
+    tt.adj = sc.adj_t;
+    tt.adj_ld = adj_ld_temporal(T);
+    tt.wf = p->conv_t.wf;
+    tt.bf = p->conv_t.bf;
+    tt.epi = tail.epi;
+    tt.xres = tail.xres;
+    tt.bn_s = tail.bn_s;
+    tt.bn_h = tail.bn_h;
+    tt.prelu = tail.prelu;
+    tt.y = y;
+    if (tail.next) {
+      const SpatialPQ m = spatial_pq_params(tail.next);
+      for (int i = 0; i < 4; ++i) {
+        tt.pqw[i] = m.w[i];
+        tt.pqb[i] = m.b[i];
+      }
+      tt.npqw = 4;
+      tt.pq = sc.pq_s;
+      tt.pql = pq_layout_vt(8, T, V);
+    }
+    tt.Vt = 0;
   }
 }
 
@@ -550,164 +603,88 @@ hipError_t tap_adjacency(const float* scratch, float* out, bool split, long rows
   return launch_tap_compact(c, s);
 }
 
-// One DSTDGCB on NTVC activations.  pq_s must already hold P/Q of x for the
-// block's two spatial DSTDGCs; the block's weight images (add_block_hl_jobs)
-// must be prepared when hl says so.
-// tap (the tap entry points only; needs the unit-parallel schedule, block_hl
-// unit): what to copy out between the launches; x must hold the block's input
-// even where the kernels do not read it (xmodel).
-hipError_t run_block(const dstd_block_params* p, const BlockFold& f, const BlockScratch& sc, int B, int T, int V,
-                     const float* x, float* h, float* y, const BlockTail& tail, hipStream_t s, Prof& pf,
-                     const BlockHL& hl, const float* xmodel = nullptr, const dstd_block_taps* tap = nullptr) {
-  BlockArgs A;
-  build_block_args(A, p, f, sc, B, T, V, x, h, y, tail, hl, xmodel);
-  const bool res = A.res;
-  if (tap && (!A.adj_launch || hl.bf || hl.tf)) return hipErrorInvalidValue;
+// One of a DSTDGCB's own launches (plan_block_launches) with its profile
+// bracket and the tap copies that follow it.  pq_s must already hold P/Q of
+// the block's input for its two spatial DSTDGCs; the block's weight images
+// (add_block_hl_jobs) must be prepared when hl says so.
+// tap (the tap entry points only; needs the unit-parallel schedule, plan_block
+// unit): what to copy out between the launches; r.x must hold the block's
+// input even where the kernels do not read it (xmodel).
+hipError_t run_block_launch(int kind, const BlockRun& r, const BlockArgs& A, const BlockPlan& hl, const BlockScratch& sc,
+                            int B, int T, int V, hipStream_t s, Prof& pf, const dstd_block_taps* tap) {
+  const BlockFold& f = *r.f;
+  const AdjHLArgs* sn = hl.next_adj ? &A.sn : nullptr;
+  if (tap && (hl.s_pre || hl.adj0 || hl.bf || hl.tf)) return hipErrorInvalidValue;
   hipError_t e = hipSuccess;
-  if (tap && tap->x) e = to_layout(x, tap->x, B, p->cin, T * V, 0, s);
-  if (e != hipSuccess) return e;
-  // (1) spatial adjacency for both graphs
-  // (s_pre: already in sc.adj_s, built by the previous block's temporal launch)
-  if (A.adj_launch) {
-    pf.begin(DSTD_KIND_ADJ_S, s);
-    e = hl.s ? launch_adj_hl(A.ah, 0, T, V, s) : launch_adj(A.aa, s);
-    pf.end(s);
-  }
-  if (e != hipSuccess) return e;
-  if (tap && tap->adj_s)
-    e = tap_adjacency(sc.adj_s, tap->adj_s, hl.s, (long)B * 2 * T, V, hl_sl_spatial(V), adj_ld_spatial(V), 0,
-                      hls(f, 5), hls(f, 6), s);
-  if (e != hipSuccess) return e;
-
-  // (2) spatial GC + bn + residual + prelu, P_t/Q_t of h
-  if (hl.s) {
-    if (!hl.bf) {  // (k_block_fused runs it with the temporal GC, step 4)
-      pf.begin(DSTD_KIND_SPATIAL, s);
-      e = launch_spatial_hl(A.ha, s);
-      pf.end(s);
+  switch (kind) {
+    case DSTD_LAUNCH_ADJ_S:  // spatial adjacency for both graphs (a tapped block's first launch)
+      if (tap && tap->x) e = to_layout(r.x, tap->x, B, r.p->cin, T * V, 0, s);
       if (e != hipSuccess) return e;
-    }
-  } else {
-  SpatialArgs sa{};
-  sa.x = x;
-  sa.B = B;
-  sa.T = T;
-  sa.V = V;
-  sa.Cin = p->cin;
-  sa.Cout = p->cout;
-  sa.NI = 2;
-  sa.G = res ? 3 : 2;
-  sa.adj = sc.adj_s;
-  sa.adj_ld = adj_ld_spatial(V);
-  for (int g = 0; g < 2; ++g) {
-    sa.wf[g] = p->conv_s[g].wf;
-    sa.bf[g] = p->conv_s[g].bf;
-  }
-  sa.wf[2] = res ? p->res_w : nullptr;
-  sa.bf[2] = res ? p->res_b : nullptr;
-  sa.epi = 1;
-  sa.bn_s = f.bn_s;
-  sa.bn_h = f.bn_h;
-  sa.rbn_s = f.rbn_s;
-  sa.rbn_h = f.rbn_h;
-  sa.prelu = p->prelu;
-  sa.y = h;
-  sa.pqw[0] = p->conv_t.wm1;
-  sa.pqw[1] = p->conv_t.wm2;
-  sa.pqb[0] = p->conv_t.bm1;
-  sa.pqb[1] = p->conv_t.bm2;
-  sa.npqw = 2;
-  sa.pq = sc.pq_t;
-  sa.pql = pq_layout_tv(4, T, V);
-  sa.Tt = 0;
-  pf.begin(DSTD_KIND_SPATIAL, s);
-  e = launch_spatial(sa, s);
-  pf.end(s);
-  if (e != hipSuccess) return e;
-  }
-  if (tap && tap->h) e = to_layout(h, tap->h, B, p->cout, T * V, 0, s);
-  if (e != hipSuccess) return e;
-
-  // (3) temporal adjacency
-  if (!hl.tf) {  // the fused temporal kernel builds its adjacency itself
-    pf.begin(DSTD_KIND_ADJ_T, s);
-    e = hl.t ? launch_adj_hl(A.aht, 1, T, V, s) : launch_adj(A.ta, s);
-    pf.end(s);
-    if (e != hipSuccess) return e;
-  }
-  if (tap && tap->adj_t)
-    e = tap_adjacency(sc.adj_t, tap->adj_t, hl.t, (long)B * V, T, hl_sl_temporal(T), adj_ld_temporal(T), 1, hls(f, 7),
-                      nullptr, s);
-  if (e != hipSuccess) return e;
-
-  // (4) temporal GC + tail epilogue (+ next block's spatial P/Q)
-  if (hl.t) {
-    if (hl.bf) {
-      pf.begin(DSTD_KIND_BLOCK, s);
-      e = launch_block_fused(A.ha, A.ht, A.aht, tail.next_adj ? &A.sn : nullptr, s,
-                             hl.adj0 && A.from_model ? &A.ah : nullptr);
+      pf.begin(DSTD_KIND_ADJ_S, s);
+      e = hl.s ? launch_adj_hl(A.ah, 0, T, V, s) : launch_adj(A.aa, s);
+      pf.end(s);
+      if (e == hipSuccess && tap && tap->adj_s)
+        e = tap_adjacency(sc.adj_s, tap->adj_s, hl.s, (long)B * 2 * T, V, hl_sl_spatial(V), adj_ld_spatial(V), 0,
+                          hls(f, 5), hls(f, 6), s);
+      return e;
+    case DSTD_LAUNCH_SPATIAL:  // spatial GC + bn + residual + prelu, P_t/Q_t of h
+      pf.begin(DSTD_KIND_SPATIAL, s);
+      e = hl.s ? launch_spatial_hl(A.ha, s) : launch_spatial(A.sa, s);
+      pf.end(s);
+      if (e == hipSuccess && tap && tap->h) e = to_layout(r.h, tap->h, B, r.p->cout, T * V, 0, s);
+      return e;
+    case DSTD_LAUNCH_ADJ_T:  // temporal adjacency
+      pf.begin(DSTD_KIND_ADJ_T, s);
+      e = hl.t ? launch_adj_hl(A.aht, 1, T, V, s) : launch_adj(A.ta, s);
+      pf.end(s);
+      if (e == hipSuccess && tap && tap->adj_t)
+        e = tap_adjacency(sc.adj_t, tap->adj_t, hl.t, (long)B * V, T, hl_sl_temporal(T), adj_ld_temporal(T), 1,
+                          hls(f, 7), nullptr, s);
+      return e;
+    case DSTD_LAUNCH_TEMPORAL:  // temporal GC + tail epilogue (+ next block's spatial P/Q)
+      pf.begin(DSTD_KIND_TEMPORAL, s);
+      e = hl.t ? launch_temporal_hl(A.ht, s) : launch_temporal(A.tt, s);
       pf.end(s);
       return e;
-    }
-    pf.begin(DSTD_KIND_TEMPORAL, s);
-    e = hl.tf ? launch_temporal_fused(A.ht, A.aht, tail.next_adj ? &A.sn : nullptr, s) : launch_temporal_hl(A.ht, s);
-    pf.end(s);
-    return e;
+    case DSTD_LAUNCH_TEMPORAL_FUSED:  // the same with its adjacency built in LDS (+ the next block's planes)
+      pf.begin(DSTD_KIND_TEMPORAL, s);
+      e = launch_temporal_fused(A.ht, A.aht, sn, s);
+      pf.end(s);
+      return e;
+    case DSTD_LAUNCH_BLOCK:  // spatial + fused temporal GC (+ block 0's own planes)
+      pf.begin(DSTD_KIND_BLOCK, s);
+      e = launch_block_fused(A.ha, A.ht, A.aht, sn, s, hl.adj0 && A.from_model ? &A.ah : nullptr);
+      pf.end(s);
+      return e;
+    default: return hipErrorInvalidValue;
   }
-  TemporalArgs tt{};
-  tt.h = h;
-  tt.B = B;
-  tt.T = T;
-  tt.V = V;
-  tt.Cin = p->cout;
-  tt.Cout = p->cout;
-  tt.adj = sc.adj_t;
-  tt.adj_ld = adj_ld_temporal(T);
-  tt.wf = p->conv_t.wf;
-  tt.bf = p->conv_t.bf;
-  tt.epi = tail.epi;
-  tt.xres = tail.xres;
-  tt.bn_s = tail.bn_s;
-  tt.bn_h = tail.bn_h;
-  tt.prelu = tail.prelu;
-  tt.y = y;
-  if (tail.next) {
-    const dstd_block_params* q = tail.next;
-    tt.pqw[0] = q->conv_s[0].wm1;
-    tt.pqw[1] = q->conv_s[0].wm2;
-    tt.pqw[2] = q->conv_s[1].wm1;
-    tt.pqw[3] = q->conv_s[1].wm2;
-    tt.pqb[0] = q->conv_s[0].bm1;
-    tt.pqb[1] = q->conv_s[0].bm2;
-    tt.pqb[2] = q->conv_s[1].bm1;
-    tt.pqb[3] = q->conv_s[1].bm2;
-    tt.npqw = 4;
-    tt.pq = sc.pq_s;
-    tt.pql = pq_layout_vt(8, T, V);
-  }
-  tt.Vt = 0;
-  pf.begin(DSTD_KIND_TEMPORAL, s);
-  e = launch_temporal(tt, s);
-  pf.end(s);
-  return e;
 }
 
-hipError_t spatial_pq(const dstd_block_params* p, const float* x_ntvc, int B, int T, int V, float* pq_s,
-                      hipStream_t s) {
+// a block's k_block_fused arguments, validated (block_fused_args), as the
+// BLOCK launch and the two chain launches take them
+hipError_t fused_args(const BlockArgs& A, const BlockPlan& hl, BlockFusedArgs* out) {
+  return block_fused_args(A.ha, A.ht, A.aht, hl.next_adj ? &A.sn : nullptr, out,
+                          hl.adj0 && A.from_model ? &A.ah : nullptr);
+}
+
+// P/Q of a block's input for its two spatial DSTDGCs.  x6 (the model's PREP
+// launch): x is the model input [B][T][V][3] and x6 = cat(x, x - x[:, -1]) is
+// written too (:298-305).
+hipError_t spatial_pq(const dstd_block_params* p, const float* x_ntvc, int B, int T, int V, float* pq_s, hipStream_t s,
+                      float* x6 = nullptr) {
+  const SpatialPQ m = spatial_pq_params(p);
   PQArgs pa{};
   pa.x = x_ntvc;
   pa.B = B;
   pa.T = T;
   pa.V = V;
   pa.Cin = p->cin;
-  pa.w[0] = p->conv_s[0].wm1;
-  pa.w[1] = p->conv_s[0].wm2;
-  pa.w[2] = p->conv_s[1].wm1;
-  pa.w[3] = p->conv_s[1].wm2;
-  pa.b[0] = p->conv_s[0].bm1;
-  pa.b[1] = p->conv_s[0].bm2;
-  pa.b[2] = p->conv_s[1].bm1;
-  pa.b[3] = p->conv_s[1].bm2;
+  pa.make_x6 = x6 ? 1 : 0;
+  pa.x6 = x6;
+  for (int i = 0; i < 4; ++i) {
+    pa.w[i] = m.w[i];
+    pa.b[i] = m.b[i];
+  }
   pa.nw = 4;
   pa.pq = pq_s;
   pa.pql = pq_layout_vt(8, T, V);
@@ -852,29 +829,12 @@ int dstd_dstdgc_fwd(int mode, const float* x, int B, int cin, int cout, int T, i
   aa.W[0] = w->wrm;
   aa.bias[0] = w->brm;
   aa.astat[0] = A;  // the caller's combined adjacency is row independent
-  aa.mode = mode;
+  adj_geometry(aa, mode, T, V);
   aa.B = B;
-  aa.T = T;
-  aa.V = V;
   aa.ngroups = 1;
   aa.alpha = alpha;
   aa.out = L.adj;
   aa.out_sG = 0;
-  if (mode == DSTD_MODE_SPATIAL) {
-    aa.nrow = T;
-    aa.K = 2 * T;
-    aa.NA = V;
-    aa.ncol = V * V;
-    aa.ldo = adj_ld_spatial(V);
-    aa.out_sN = (long)T * aa.ldo;
-  } else {
-    aa.nrow = V;
-    aa.K = 2 * V;
-    aa.NA = T;
-    aa.ncol = T * T;
-    aa.ldo = adj_ld_temporal(T);
-    aa.out_sN = (long)V * aa.ldo;
-  }
   DSTD_TRY(launch_adj(aa, s));
   if (mode == DSTD_MODE_SPATIAL) {
     SpatialArgs sa{};
@@ -952,21 +912,26 @@ int block_fwd(const dstd_block_params* p, const float* x, int B, int T, int V, f
   Carver cv{(char*)workspace};
   BlockLayout L;
   carve_block(cv, L, B, p->cin, p->cout, T, V);
+  Plan pl;
+  plan_single_block(pl, p->cin, p->cout, B, T, V, hl_device_cus(), flags, taps != nullptr);
+  const BlockRun r{p, &L.f, L.xin, L.h, L.yout, BlockTail{TEPI_RAW, nullptr, nullptr, nullptr, nullptr, nullptr}};
   FoldList fa;
   add_block_jobs(fa, p, L.f, T, V);
   DSTD_TRY(run_fold(fa, s));
   DSTD_TRY(to_layout(x, L.xin, B, p->cin, T * V, 1, s));
   DSTD_TRY(spatial_pq(p, L.xin, B, T, V, L.sc.pq_s, s));
-  BlockTail tail{TEPI_RAW, nullptr, nullptr, nullptr, nullptr, nullptr};
-  const BlockHL hl = block_hl(p, tail, B, T, V, flags, taps != nullptr);
   HLList hj;
-  add_block_hl_jobs(hj, p, L.f, tail, hl, T, V);
+  add_block_hl_jobs(hj, p, L.f, r.tail, pl.blk[0], T, V);
   DSTD_TRY(run_hl_prep(hj, s));
+  BlockArgs A;
+  build_block_args(A, r, L.sc, B, T, V, pl.blk[0], nullptr);
   Prof pf;
-  DSTD_TRY(run_block(p, L.f, L.sc, B, T, V, L.xin, L.h, L.yout, tail, s, pf, hl, nullptr, taps));
+  for (int i = 0; i < pl.n; ++i)
+    DSTD_TRY(run_block_launch(pl.launch[i].kind, r, A, pl.blk[0], L.sc, B, T, V, s, pf, taps));
   DSTD_TRY(to_layout(L.yout, y, B, p->cout, T * V, 0, s));
   return DSTD_OK;
 }
+
 
 }  // namespace
 
@@ -984,10 +949,21 @@ int dstd_model_fwd_profiled(const dstd_model_params* p, const float* x, int B, f
 
 int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* y, void* workspace,
                       size_t workspace_bytes, void* stream, unsigned flags, dstd_profile* prof) {
-  if (flags & ~(DSTD_FWD_REUSE_CONSTANTS | DSTD_FWD_EXACT_FP32 | DSTD_FWD_SEPARATE_ADJ | DSTD_FWD_FUSED_TEMPORAL |
-                DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS | DSTD_FWD_SEPARATE_ENDS))
-    return DSTD_EINVAL;
+  if (flags & ~kModelFwdFlags) return DSTD_EINVAL;
   return model_fwd(p, x, B, y, workspace, workspace_bytes, stream, flags, prof, nullptr);
+}
+
+int dstd_model_fwd_schedule(int B, int T, int V, int num_feature, int num_layers, unsigned flags, int profiled,
+                            int taps, int cus, dstd_launch* out, int capacity) {
+  // taps: dstd_model_fwd_taps, which takes DSTD_FWD_EXACT_FP32 only and no profile
+  if ((flags & ~((taps & 1) ? DSTD_FWD_EXACT_FP32 : kModelFwdFlags)) || (taps & ~3) || taps == 2 ||
+      ((taps & 1) && profiled) || capacity < 0 || (capacity > 0 && !out))
+    return DSTD_EINVAL;
+  if (const int e = model_shape_code(B, T, V, num_feature, num_layers)) return e;
+  Plan pl;
+  plan_model(pl, B, T, V, num_feature, num_layers, cus > 0 ? cus : hl_device_cus(), flags, profiled != 0, taps);
+  for (int i = 0; i < pl.n && i < capacity; ++i) out[i] = pl.launch[i];
+  return pl.n;
 }
 
 size_t dstd_model_taps_workspace_bytes(int B, int T, int V, int num_feature, int num_layers) {
@@ -1009,16 +985,13 @@ namespace {
 // block's taps copied out between its launches
 int model_fwd(const dstd_model_params* p, const float* x, int B, float* y, void* workspace, size_t workspace_bytes,
               void* stream, unsigned flags, dstd_profile* prof, const dstd_block_taps* taps) {
+  // (1) arguments
   StreamDeviceGuard dev_guard_(stream, x);
-  if (taps) flags |= DSTD_FWD_SEPARATE_ADJ | DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS;
-  const bool reuse = (flags & DSTD_FWD_REUSE_CONSTANTS) != 0;
   if (!p || !x || !y || !workspace) return DSTD_EINVAL;
   if (prof && (prof->capacity < 0 || (prof->capacity > 0 && (!prof->events || !prof->kinds)))) return DSTD_EINVAL;
-  Prof pf;
-  pf.p = prof;
-  const int T = p->T, V = p->V, C = p->num_feature, L_ = p->num_layers;
-  if (!shape_ok(B, T, V) || L_ < 0 || L_ > DSTD_MAX_LAYERS || p->in_channels != 6) return DSTD_EINVAL;
-  if (!limits_ok(T, V, p->in_channels, C)) return DSTD_ELIMIT;
+  const int T = p->T, V = p->V, C = p->num_feature, L_ = p->num_layers, NB = L_ + 2;
+  if (p->in_channels != 6) return DSTD_EINVAL;
+  if (const int e = model_shape_code(B, T, V, C, L_)) return e;
   if (!block_ok(&p->st_in) || !block_ok(&p->st_out) || !bn_ok(p->bn_in) || !p->prelu) return DSTD_EINVAL;
   if (p->st_in.cin != 6 || p->st_in.cout != C || p->st_out.cin != C || p->st_out.cout != 3) return DSTD_EINVAL;
   for (int i = 0; i < L_; ++i) {
@@ -1026,185 +999,113 @@ int model_fwd(const dstd_model_params* p, const float* x, int B, float* y, void*
     if (p->enc[i].cin != C || p->enc[i].cout != C) return DSTD_EINVAL;
   }
   if (workspace_bytes < dstd_model_workspace_bytes(B, T, V, C, L_)) return DSTD_EWORKSPACE;
+
+  // (2) workspace
   hipStream_t s = (hipStream_t)stream;
   Carver cv{(char*)workspace};
   ModelLayout L;
   carve_model(cv, L, B, T, V, C, L_, 6, 3);
 
-  FoldList fa;
-  add_block_jobs(fa, &p->st_in, L.f_in, T, V);
-  add_block_jobs(fa, &p->st_out, L.f_out, T, V);
-  add_bn_job(fa, p->bn_in, C, V, L.bnin_s, L.bnin_h);
-  for (int i = 0; i < L_; ++i) {
-    add_block_jobs(fa, &p->enc[i], L.f_enc[i], T, V);
-    add_bn_job(fa, p->enc_bn[i], C, V, L.ebn_s[i], L.ebn_h[i]);
-  }
-  if (!reuse) {
-    pf.begin(DSTD_KIND_FOLD, s);
-    DSTD_TRY(run_fold(fa, s));
-    pf.end(s);
-  }
+  // (3) plan
+  Plan pl;
+  plan_model(pl, B, T, V, C, L_, hl_device_cus(), flags, prof && prof->capacity > 0,
+             taps ? 1 | (taps[0].x ? 2 : 0) : 0);
+  const dstd_launch* first = pl.launch + (pl.prep ? 1 : 0);  // (PREP: step 4)
+  const bool one_launch = first->kind == DSTD_LAUNCH_MODEL;
 
   // conv_st_in -> bn_in -> prelu (dropout is identity in eval); encoders
   // x = prelu_e(bn_e(DSTDGCB(x) + x)); conv_st_out + output residual written
   // straight into y [B][T][V][3].  Buffers rotate over act[0..2].
-  const int NB = L_ + 2;
-  const dstd_block_params* blk[DSTD_MAX_LAYERS + 2];
-  const BlockFold* fold[DSTD_MAX_LAYERS + 2];
-  BlockTail tails[DSTD_MAX_LAYERS + 2];
-  BlockHL hls[DSTD_MAX_LAYERS + 2];
-  const float* xin[DSTD_MAX_LAYERS + 2];
-  float* hbuf[DSTD_MAX_LAYERS + 2];
-  float* ybuf[DSTD_MAX_LAYERS + 2];
-  {
-    float* cur = L.act[0];
-    float* h = L.act[1];
-    float* out = L.act[2];
-    blk[0] = &p->st_in;
-    fold[0] = &L.f_in;
-    tails[0] = BlockTail{TEPI_IN, nullptr, L.bnin_s, L.bnin_h, p->prelu, L_ > 0 ? &p->enc[0] : &p->st_out};
-    xin[0] = cur;
-    hbuf[0] = h;
-    ybuf[0] = out;
-    for (int i = 0; i < L_; ++i) {
-      float* xi = out;
-      float* hh = cur;
-      float* yy = h;
-      blk[1 + i] = &p->enc[i];
-      fold[1 + i] = &L.f_enc[i];
-      tails[1 + i] = BlockTail{TEPI_ENC, xi, L.ebn_s[i], L.ebn_h[i], p->enc_prelu[i], i + 1 < L_ ? &p->enc[i + 1] : &p->st_out};
-      xin[1 + i] = xi;
-      hbuf[1 + i] = hh;
-      ybuf[1 + i] = yy;
-      cur = xi;
-      h = hh;
-      out = yy;
-    }
-    blk[NB - 1] = &p->st_out;
-    fold[NB - 1] = &L.f_out;
-    tails[NB - 1] = BlockTail{TEPI_OUT, x, nullptr, nullptr, nullptr, nullptr};
-    xin[NB - 1] = out;
-    hbuf[NB - 1] = h;
-    ybuf[NB - 1] = y;
+  BlockRun run[kPlanMaxBlocks];
+  float *cur = L.act[0], *h = L.act[1], *out = L.act[2];
+  run[0] = BlockRun{&p->st_in, &L.f_in, cur, h, out, BlockTail{TEPI_IN, nullptr, L.bnin_s, L.bnin_h, p->prelu, nullptr}};
+  for (int i = 0; i < L_; ++i) {
+    float* t = cur;  // x: the previous block's y, h: its x, y: its h
+    cur = out;
+    out = h;
+    h = t;
+    run[1 + i] = BlockRun{&p->enc[i], &L.f_enc[i], cur, h, out,
+                          BlockTail{TEPI_ENC, cur, L.ebn_s[i], L.ebn_h[i], p->enc_prelu[i], nullptr}};
   }
-  HLList hj;
-  for (int b = 0; b < NB; ++b) {
-    hls[b] = block_hl(blk[b], tails[b], B, T, V, flags, taps != nullptr);
-    add_block_hl_jobs(hj, blk[b], *fold[b], tails[b], hls[b], T, V);
+  // conv_st_out's h is [B][T][V][3]: in an act buffer, sample n's rows lie
+  // inside the 64-channel slice of sample 3n / 64, which that sample's
+  // workgroup may still be reading or writing as an encoder block's
+  // activation -- between launches every encoder block was over before
+  // conv_st_out began.  In the one-launch schedule it goes to the temporal
+  // adjacency scratch, which no launch of that schedule touches (every
+  // temporal adjacency is built in LDS) and which holds B V T T floats or more.
+  run[NB - 1] = BlockRun{&p->st_out, &L.f_out, out, one_launch ? L.sc.adj_t : h, y,
+                         BlockTail{TEPI_OUT, x, nullptr, nullptr, nullptr, nullptr}};
+  for (int b = 0; b + 1 < NB; ++b) {
+    run[b].tail.next = run[b + 1].p;
+    run[b].tail.next_f = run[b + 1].f;
   }
-  // a block's spatial adjacency from the previous block's fused temporal
-  // launch (phase 3), which writes the P/Q it is built from
-  for (int b = 1; b < NB && !(flags & DSTD_FWD_SEPARATE_ADJ); ++b)
-    if (hls[b].s && hls[b - 1].tf && blk[b - 1]->cout == 64 && temporal_fused_phase3(T, V)) {
-      hls[b].s_pre = true;
-      tails[b - 1].next_f = fold[b];
-      tails[b - 1].next_adj = true;
-    }
-  // block 0's spatial planes (from the model input) inside its block launch
-  // rather than a k_adj_hl<0> launch of their own
-  if (hls[0].bf && !(flags & DSTD_FWD_SEPARATE_ADJ) && blk[0]->cin == 6 && block_fused_adj0_supported(T, V))
-    hls[0].adj0 = true;
 
-  // input prep: x6 = cat(x, x - x[:, -1]) and block-0 spatial P/Q (:298-305)
-  PQArgs pa{};
-  pa.x = x;
-  pa.B = B;
-  pa.T = T;
-  pa.V = V;
-  pa.Cin = 6;
-  pa.make_x6 = 1;
-  pa.x6 = L.act[0];
-  const dstd_block_params* b0 = &p->st_in;
-  pa.w[0] = b0->conv_s[0].wm1;
-  pa.w[1] = b0->conv_s[0].wm2;
-  pa.w[2] = b0->conv_s[1].wm1;
-  pa.w[3] = b0->conv_s[1].wm2;
-  pa.b[0] = b0->conv_s[0].bm1;
-  pa.b[1] = b0->conv_s[0].bm2;
-  pa.b[2] = b0->conv_s[1].bm1;
-  pa.b[3] = b0->conv_s[1].bm2;
-  pa.nw = 4;
-  pa.pq = L.sc.pq_s;
-  pa.pql = pq_layout_vt(8, T, V);
-  // the split kernels build x6 and these P/Q from x themselves (a tap of
-  // block 0's input still needs x6 in memory)
-  if (!hls[0].s || (taps && taps[0].x)) {
-    pf.begin(DSTD_KIND_PREP, s);
-    DSTD_TRY(launch_pq(pa, s));
+  // (4) constants (DSTD_FWD_REUSE_CONSTANTS: still in the workspace) and PREP
+  Prof pf;
+  pf.p = prof;
+  const bool reuse = (flags & DSTD_FWD_REUSE_CONSTANTS) != 0;
+  if (!reuse) {
+    FoldList fa;
+    add_block_jobs(fa, &p->st_in, L.f_in, T, V);
+    add_block_jobs(fa, &p->st_out, L.f_out, T, V);
+    add_bn_job(fa, p->bn_in, C, V, L.bnin_s, L.bnin_h);
+    for (int i = 0; i < L_; ++i) {
+      add_block_jobs(fa, &p->enc[i], L.f_enc[i], T, V);
+      add_bn_job(fa, p->enc_bn[i], C, V, L.ebn_s[i], L.ebn_h[i]);
+    }
+    pf.begin(DSTD_KIND_FOLD, s);
+    DSTD_TRY(run_fold(fa, s));
     pf.end(s);
   }
-
+  if (pl.prep) {
+    pf.begin(DSTD_KIND_PREP, s);
+    DSTD_TRY(spatial_pq(&p->st_in, x, B, T, V, L.sc.pq_s, s, L.act[0]));
+    pf.end(s);
+  }
   if (!reuse) {
+    HLList hj;
+    for (int b = 0; b < NB; ++b) add_block_hl_jobs(hj, run[b].p, *run[b].f, run[b].tail, pl.blk[b], T, V);
     pf.begin(DSTD_KIND_FOLD, s);
     DSTD_TRY(run_hl_prep(hj, s));
     pf.end(s);
   }
-  // A run of consecutive encoder blocks as one launch (k_enc_chain): blocks
-  // that would each run k_block_fused on planes from the previous launch.
-  // Not in a profiled call: its event brackets are per block.
-  const bool chain = !(flags & (DSTD_FWD_SEPARATE_ENCODERS | DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ADJ)) &&
-                     !(prof && prof->capacity > 0) && enc_chain_supported(T, V);
-  auto chain_block = [&](int b, EncChainArgs* c) {
-    if (!chain || b < 1 || b > L_ || !hls[b].bf || !hls[b].s_pre || !tails[b].next_adj) return false;
-    BlockArgs A;
-    build_block_args(A, blk[b], *fold[b], L.sc, B, T, V, xin[b], hbuf[b], ybuf[b], tails[b], hls[b], nullptr);
+
+  // (5) the plan's launches
+  BlockArgs A[kPlanMaxBlocks];
+  for (int b = 0; b < NB; ++b) build_block_args(A[b], run[b], L.sc, B, T, V, pl.blk[b], b == 0 ? x : nullptr);
+  for (const dstd_launch* l = first; l < pl.launch + pl.n; ++l) {
+    const int b0 = l->first_block, b1 = b0 + l->num_blocks;
     BlockFusedArgs ba;
-    return block_fused_args(A.ha, A.ht, A.aht, &A.sn, &ba, nullptr) == hipSuccess &&
-           enc_chain_append(c, ba) == hipSuccess;
-  };
-  // The whole forward as one launch (k_model_chain): conv_st_in with its own
-  // planes (adj0), 1..kModelChainMaxEnc encoder blocks that would form one run,
-  // conv_st_out on planes from the last encoder block's phase 3.
-  auto model_chain = [&](ModelChainArgs* c) {
-    if (!chain || (flags & DSTD_FWD_SEPARATE_ENDS) || taps || L_ < 1 || L_ > kModelChainMaxEnc ||
-        !model_chain_supported(T, V) || !hls[0].bf || !hls[0].adj0 || !tails[0].next_adj || !hls[NB - 1].bf ||
-        !hls[NB - 1].s_pre)
-      return false;
-    for (int b = 1; b <= L_; ++b)  // (chain_block's test; model_chain_append validates as enc_chain_append)
-      if (!hls[b].bf || !hls[b].s_pre || !tails[b].next_adj) return false;
-    for (int i = 0; i < NB; ++i) {
-      const int b = i < L_ ? 1 + i : i == L_ ? 0 : NB - 1;  // encoder blocks, conv_st_in, conv_st_out
-      // conv_st_out's h is [B][T][V][3]: in an act buffer, sample n's rows lie
-      // inside the 64-channel slice of sample 3n / 64, which that sample's
-      // workgroup may still be reading or writing as an encoder block's
-      // activation -- between launches every encoder block was over before
-      // conv_st_out began.  Here it goes to the temporal adjacency scratch,
-      // which no launch of this schedule touches (every temporal adjacency is
-      // built in LDS) and which holds B V T T floats or more.
-      float* hb = b == NB - 1 ? L.sc.adj_t : hbuf[b];
-      BlockArgs A;
-      build_block_args(A, blk[b], *fold[b], L.sc, B, T, V, xin[b], hb, ybuf[b], tails[b], hls[b], b == 0 ? x : nullptr);
-      BlockFusedArgs ba;
-      if (block_fused_args(A.ha, A.ht, A.aht, tails[b].next_adj ? &A.sn : nullptr, &ba,
-                           b == 0 && A.from_model ? &A.ah : nullptr) != hipSuccess ||
-          model_chain_append(c, ba) != hipSuccess)
-        return false;
+    if (taps && l->num_blocks != 1) return hipErrorInvalidValue;
+    switch (l->kind) {
+      case DSTD_LAUNCH_MODEL: {
+        ModelChainArgs c{};  // the encoder blocks set the shared geometry: they go first
+        for (int i = 0; i < NB; ++i) {
+          const int b = i < L_ ? 1 + i : i == L_ ? 0 : NB - 1;
+          DSTD_TRY(fused_args(A[b], pl.blk[b], &ba));
+          DSTD_TRY(model_chain_append(&c, ba));
+        }
+        DSTD_TRY(launch_model_chain(c, s));
+        break;
+      }
+      case DSTD_LAUNCH_ENC_RUN: {
+        EncChainArgs c{};
+        for (int b = b0; b < b1; ++b) {
+          DSTD_TRY(fused_args(A[b], pl.blk[b], &ba));
+          DSTD_TRY(enc_chain_append(&c, ba));
+        }
+        DSTD_TRY(launch_enc_chain(c, s));
+        break;
+      }
+      default:
+        pf.block = b0;
+        DSTD_TRY(run_block_launch(l->kind, run[b0], A[b0], pl.blk[b0], L.sc, B, T, V, s, pf, taps ? &taps[b0] : nullptr));
     }
-    return model_chain_complete(*c);
-  };
-  {
-    ModelChainArgs mc{};
-    if (model_chain(&mc)) {
-      DSTD_TRY(launch_model_chain(mc, s));
-      return DSTD_OK;
-    }
-  }
-  for (int b = 0; b < NB;) {
-    EncChainArgs c{};
-    int e = b;
-    while (e < NB && chain_block(e, &c)) ++e;
-    if (e - b >= 2) {
-      DSTD_TRY(launch_enc_chain(c, s));
-      b = e;
-      continue;
-    }
-    pf.block = b;
-    DSTD_TRY(run_block(blk[b], *fold[b], L.sc, B, T, V, xin[b], hbuf[b], ybuf[b], tails[b], s, pf, hls[b],
-                       b == 0 ? x : nullptr, taps ? &taps[b] : nullptr));
-    ++b;
   }
   return DSTD_OK;
 }
+
 
 }  // namespace
 

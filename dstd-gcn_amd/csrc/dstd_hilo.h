@@ -493,7 +493,8 @@ bool enc_chain_supported(int T, int V);
 // appends one validated encoder block (block_fused_args) to the run; the first
 // one sets the shared geometry.  hipErrorNotSupported when the block is no
 // 64 -> 64 ENC block with phase 3, differs from the run in anything but its
-// descriptor, or the run is full: the caller launches it on its own instead
+// descriptor, or the run is full: the planner (dstd_plan.h) chooses runs that
+// pass, so to the caller a rejection is an error
 hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a);
 hipError_t launch_enc_chain(const EncChainArgs& c, hipStream_t s);
 
@@ -588,7 +589,7 @@ bool model_chain_supported(int T, int V);
 // shared geometry), then conv_st_in (with s0) and conv_st_out in either order.
 // hipErrorNotSupported when the block is none of the three kinds, differs from
 // the shared geometry in anything outside its compact form, or its place is
-// taken: the caller keeps its launches per block / per run
+// taken (an error to the caller, as for enc_chain_append)
 hipError_t model_chain_append(ModelChainArgs* c, const BlockFusedArgs& a);
 // conv_st_in, at least one encoder block and conv_st_out are in place
 bool model_chain_complete(const ModelChainArgs& c);

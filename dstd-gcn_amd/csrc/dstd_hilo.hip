@@ -3179,16 +3179,24 @@ static bool enc_chain_same_geometry(const BlockFusedArgs& a, const SpatialHLArgs
 }
 static EncChainDesc enc_chain_desc(const BlockFusedArgs& a);
 
-hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a) {
-  if (!enc_chain_kind_ok(a)) return hipErrorNotSupported;
-  if (c->nblk == 0) {
-    c->s = a.s;
-    c->t = a.t;
-  } else if (c->nblk >= kEncChainMax || !enc_chain_same_geometry(a, c->s, c->t)) {
+// One more encoder block for a launch that carries the shared geometry (s, t:
+// the first block's arguments) and a descriptor per block (enc[0..n) of cap):
+// k_enc_chain's run and k_model_chain's encoder stack alike.
+static hipError_t chain_append_enc(SpatialHLArgs& s, TemporalFusedArgs& t, EncChainDesc* enc, int& n, int cap,
+                                   const BlockFusedArgs& a) {
+  if (n >= cap || !enc_chain_kind_ok(a)) return hipErrorNotSupported;
+  if (n == 0) {
+    s = a.s;
+    t = a.t;
+  } else if (!enc_chain_same_geometry(a, s, t)) {
     return hipErrorNotSupported;
   }
-  c->enc[c->nblk++] = enc_chain_desc(a);
+  enc[n++] = enc_chain_desc(a);
   return hipSuccess;
+}
+
+hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a) {
+  return chain_append_enc(c->s, c->t, c->enc, c->nblk, kEncChainMax, a);
 }
 
 // the descriptor fields of a block's arguments (for conv_st_out, which has no
@@ -3269,18 +3277,8 @@ hipError_t model_chain_append(ModelChainArgs* c, const BlockFusedArgs& a) {
   if (!model_chain_supported(g.T, g.V)) return hipErrorNotSupported;
   const bool enc = s.Cin == 64 && s.Cout == 64 && g.epi == TEPI_ENC;
   const bool in = s.Cin == 6 && s.Cout == 64 && g.epi == TEPI_IN, out = s.Cin == 64 && s.Cout == 3 && g.epi == TEPI_OUT;
-  if (enc) {
-    // the encoder blocks exactly as a run of k_enc_chain takes them
-    if (c->have || c->nenc >= kModelChainMaxEnc || !enc_chain_kind_ok(a)) return hipErrorNotSupported;
-    if (c->nenc == 0) {
-      c->s = s;
-      c->t = a.t;
-    } else if (!enc_chain_same_geometry(a, c->s, c->t)) {
-      return hipErrorNotSupported;
-    }
-    c->enc[c->nenc++] = enc_chain_desc(a);
-    return hipSuccess;
-  }
+  // the encoder blocks exactly as a run of k_enc_chain takes them, before the ends
+  if (enc) return c->have ? hipErrorNotSupported : chain_append_enc(c->s, c->t, c->enc, c->nenc, kModelChainMaxEnc, a);
   if (!(in || out) || c->nenc < 1 || (c->have & (in ? 1 : 2))) return hipErrorNotSupported;
   // everything outside the compact form is the shared geometry
   const SpatialHLArgs& sg = c->s;

@@ -52,6 +52,11 @@ class Profile(ctypes.Structure):
                 ("block", ctypes.POINTER(ctypes.c_int)), ("only_block", ctypes.c_int)]
 
 
+class Launch(ctypes.Structure):
+    """include/dstd_gcn.h dstd_launch: one entry of a forward's launch schedule."""
+    _fields_ = [("kind", ctypes.c_int), ("first_block", ctypes.c_int), ("num_blocks", ctypes.c_int)]
+
+
 class BlockTaps(ctypes.Structure):
     """include/dstd_gcn_taps.h dstd_block_taps: where one DSTDGCB's taps go
     (device pointers to dense fp32; None: not wanted, not written)."""
@@ -117,6 +122,20 @@ FWD_SEPARATE_ENCODERS = 32  # include/dstd_gcn.h DSTD_FWD_SEPARATE_ENCODERS
 FWD_SEPARATE_ENDS = 64  # include/dstd_gcn.h DSTD_FWD_SEPARATE_ENDS
 KIND_FOLD, KIND_PREP, KIND_ADJ_S, KIND_SPATIAL, KIND_ADJ_T, KIND_TEMPORAL, KIND_BLOCK = range(7)
 KIND_NAMES = ("fold", "prep", "adj_spatial", "spatial_gc", "adj_temporal", "temporal_gc", "block")
+# include/dstd_gcn.h DSTD_LAUNCH_*: the kinds of a launch schedule's entries
+(LAUNCH_PREP, LAUNCH_ADJ_S, LAUNCH_SPATIAL, LAUNCH_ADJ_T, LAUNCH_TEMPORAL, LAUNCH_TEMPORAL_FUSED, LAUNCH_BLOCK,
+ LAUNCH_ENC_RUN, LAUNCH_MODEL) = range(9)
+
+
+def model_schedule(B, T, V, num_feature, num_layers, flags=0, profiled=False, taps=0, cus=0):
+    """dstd_model_fwd_schedule: the (kind, first_block, num_blocks) launches a
+    forward of these arguments enqueues after its parameter preparation; cus=0:
+    on the current device.  With cus > 0 no GPU is touched."""
+    out = (Launch * (1 + 4 * (MAX_LAYERS + 2)))()
+    n = lib().dstd_model_fwd_schedule(B, T, V, num_feature, num_layers, flags, int(profiled), taps, cus, out, len(out))
+    if n < 0:
+        raise RuntimeError(f"dstd_model_fwd_schedule failed ({n}): {lib().dstd_error_string(n).decode()}")
+    return [(out[i].kind, out[i].first_block, out[i].num_blocks) for i in range(n)]
 
 _lib = None
 
@@ -181,6 +200,10 @@ def lib():
         L.dstd_model_fwd_profiled.restype = ci
         L.dstd_model_fwd_profiled.argtypes = [ctypes.POINTER(ModelParams), vp, ci, vp, vp, sz, vp,
                                               ctypes.POINTER(Profile)]
+        # (absent from an earlier revision's library loaded for an A/B)
+        if hasattr(L, "dstd_model_fwd_schedule"):
+            L.dstd_model_fwd_schedule.restype = ci
+            L.dstd_model_fwd_schedule.argtypes = [ci] * 5 + [ctypes.c_uint, ci, ci, ci, ctypes.POINTER(Launch), ci]
         L.dstd_events_create.restype = ci
         L.dstd_events_create.argtypes = [ci, ctypes.POINTER(ctypes.c_void_p)]
         L.dstd_events_destroy.restype = ci
@@ -283,7 +306,7 @@ def lib():
 EXPORTS = ("dstd_version", "dstd_source_hash", "dstd_error_string", "dstd_dstdgc_workspace_bytes", "dstd_block_workspace_bytes",
            "dstd_model_workspace_bytes", "dstd_dstdgc_fwd", "dstd_block_fwd", "dstd_model_fwd",
            "dstd_model_fwd_profiled", "dstd_events_create", "dstd_events_destroy", "dstd_event_elapsed_ms",
-           "dstd_block_fwd_ex", "dstd_model_fwd_ex")
+           "dstd_block_fwd_ex", "dstd_model_fwd_ex", "dstd_model_fwd_schedule")
 TRAIN_EXPORTS = ("dstd_dstdgc_train_saved_bytes", "dstd_dstdgc_train_workspace_bytes", "dstd_dstdgc_train_fwd",
                  "dstd_dstdgc_train_bwd", "dstd_block_train_saved_bytes", "dstd_block_train_workspace_bytes",
                  "dstd_block_train_fwd", "dstd_block_train_bwd", "dstd_model_train_saved_bytes",

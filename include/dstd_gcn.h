@@ -233,6 +233,26 @@ int dstd_model_fwd_profiled(const dstd_model_params* p, const float* x, int B, f
 #define DSTD_FWD_SEPARATE_ENDS 64u
 int dstd_model_fwd_ex(const dstd_model_params* p, const float* x, int B, float* y, void* workspace,
                       size_t workspace_bytes, void* stream, unsigned flags, dstd_profile* prof);
+
+/* The launch schedule ("Launch schedule").  first_block and
+ * num_blocks: the DSTDGCBs a launch covers (conv_st_in 0, the encoders
+ * 1..num_layers, conv_st_out num_layers + 1); PREP: -1, 0. */
+#define DSTD_LAUNCH_PREP 0           /* x6 = cat(x, x - x[:, -1]) and block 0's spatial P/Q */
+#define DSTD_LAUNCH_ADJ_S 1          /* a block's spatial adjacencies */
+#define DSTD_LAUNCH_SPATIAL 2        /* its spatial GC */
+#define DSTD_LAUNCH_ADJ_T 3          /* its temporal adjacency */
+#define DSTD_LAUNCH_TEMPORAL 4       /* its temporal GC on that adjacency */
+#define DSTD_LAUNCH_TEMPORAL_FUSED 5 /* its temporal GC with the adjacency built in LDS */
+#define DSTD_LAUNCH_BLOCK 6          /* the whole block */
+#define DSTD_LAUNCH_ENC_RUN 7        /* num_blocks consecutive encoder blocks */
+#define DSTD_LAUNCH_MODEL 8          /* the whole forward */
+typedef struct { int kind, first_block, num_blocks; } dstd_launch;
+/* the launches dstd_model_fwd_ex would enqueue after the parameter preparation;
+ * profiled: the call carries a profile with capacity > 0; taps (dstd_model_fwd_taps,
+ * dstd_gcn_taps.h): bit 0 tapped, bit 1 block 0's input is tapped;
+ * cus <= 0: the current device's. Returns the count (may exceed capacity), or DSTD_E*. */
+int dstd_model_fwd_schedule(int B, int T, int V, int num_feature, int num_layers, unsigned flags,
+                            int profiled, int taps, int cus, dstd_launch* out, int capacity);
 int dstd_events_create(int n, void** events);
 int dstd_events_destroy(int n, void** events);
 int dstd_event_elapsed_ms(void* start, void* stop, float* ms);

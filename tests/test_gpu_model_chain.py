@@ -40,9 +40,35 @@ def load_model(tag):
     return m.to(DEV).eval(), opts
 
 
+def expected_plans(layers):
+    """(default, DSTD_FWD_SEPARATE_ENDS, DSTD_FWD_SEPARATE_ENCODERS) launch lists
+    of a forward whose every block can be a whole-block launch: one MODEL launch
+    for 1..MAX_ENC encoder blocks; conv_st_in, the encoder runs (at most 8 blocks
+    each, a left-over single block on its own), conv_st_out; one BLOCK per block."""
+    per_block = [(native.LAUNCH_BLOCK, b, 1) for b in range(layers + 2)]
+    runs, b = per_block[:1], 1
+    while b <= layers:
+        n = min(8, layers + 1 - b)
+        runs.append((native.LAUNCH_ENC_RUN, b, n) if n >= 2 else per_block[b])
+        b += n
+    runs.append(per_block[-1])
+    return ([(native.LAUNCH_MODEL, 0, layers + 2)] if 1 <= layers <= MAX_ENC else runs), runs, per_block
+
+
+def planned(m, x, flags):
+    """dstd_model_fwd_schedule for m(x) with these flags on this device."""
+    B, T, V, _ = x.shape
+    return native.model_schedule(B, T, V, 64, len(m.encoders), flags)
+
+
 def three(m, x, flags):
     """(one launch, conv_st_in + encoder run + conv_st_out, one launch per block) outputs of one input."""
     ys = [torch.empty_like(x) for _ in range(3)]
+    want = expected_plans(len(m.encoders))
+    for extra, w in zip((0, native.FWD_SEPARATE_ENDS, native.FWD_SEPARATE_ENCODERS), want):
+        assert planned(m, x, flags | extra) == w, (extra, planned(m, x, flags | extra))
+    if 1 <= len(m.encoders) <= MAX_ENC:  # else the default falls back to the runs
+        assert want[0] != want[1] and want[0] != want[2]
     with torch.no_grad():
         for y, extra in zip(ys, (0, native.FWD_SEPARATE_ENDS, native.FWD_SEPARATE_ENCODERS)):
             m._forward_native(x, y, arith=flags | extra)
@@ -132,6 +158,7 @@ def test_model_chain_graph_replay():
     Tin = opts["input_time_frame"]
     T = Tin + opts["output_time_frame"]
     x1, x2 = synth(32, T, 22, Tin, 171).to(DEV), synth(32, T, 22, Tin, 172).to(DEV)
+    assert planned(m, x1, m._dstd_fwd_flags) == [(native.LAUNCH_MODEL, 0, opts["num_layers"] + 2)]
     with torch.no_grad():
         run = m.graphed(x1, frozen=True)
         y1 = run(x1).clone()  # folds
