@@ -1,0 +1,339 @@
+"""Device-resident dataset and loader (include/dstd_gcn_data.h).
+
+The reference feeds its engine from a ``torch.utils.data.DataLoader`` over four
+float64 host arrays (``dataset/h36m.py:47-64``, ``cmu.py``, ``pw3d.py``): every
+step casts and copies three of them to the GPU.  Those arrays are selections
+of one -- frames and columns of ``all_seqs`` -- and its windows overlap T-fold.
+``DeviceSequences`` keeps the distinct frames in device memory once, as
+``float32(float64 value)`` (what the engine's per-batch ``.float()`` gives), and
+``DeviceLoader`` yields the reference's 4-tuple ``(inputs, inputs_inv, targets,
+all_seqs)`` as contiguous fp32 device tensors, one ``dstd_batch_gather`` launch
+per batch: no DataLoader, no worker processes, no host-to-device copy and no
+host synchronisation per step.  ``PredictionEngine.train`` / ``test`` take the
+loader as they take the reference's.
+
+There is no CPU gather: a set built with ``device="cpu"`` serves the host-side
+bookkeeping (weights, window starts, index order) only.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+import dstd_native as native
+
+
+def frame_maps(input_n, output_n, padding=True):
+    """(i_idx, i_idx_inv) of the datasets (dataset/h36m.py:53-60): which window
+    frame each frame of ``inputs`` / ``inputs_inv`` is.  With padding the
+    output part repeats the last input frame (of the reversed window: frame
+    output_n); without, the window itself and its reversal."""
+    T = input_n + output_n
+    if input_n < 1 or output_n < 0:
+        raise ValueError(f"frame_maps: input_n {input_n}, output_n {output_n}")
+    if padding:
+        fwd = np.concatenate([np.arange(input_n), np.full(output_n, input_n - 1)])
+        inv = np.concatenate([np.arange(output_n, T)[::-1], np.full(output_n, output_n)])
+    else:
+        fwd = np.arange(T)
+        inv = fwd[::-1]
+    return fwd.astype(np.int32), np.ascontiguousarray(inv).astype(np.int32)
+
+
+def mirror_source(n_joints, left, right):
+    """mirror_src of get_mirror (dataset/h36m.py:100-116) for the caller's
+    joint lists: joint j of a mirrored window reads joint mirror_src[j]."""
+    left, right = np.asarray(left, dtype=np.int64), np.asarray(right, dtype=np.int64)
+    if left.shape != right.shape or left.ndim != 1:
+        raise ValueError("mirror: left and right joint lists of equal length")
+    if len(left) and (min(left.min(), right.min()) < 0 or max(left.max(), right.max()) >= n_joints):
+        raise ValueError(f"mirror: joint outside 0..{n_joints - 1}")
+    ident = np.arange(n_joints)
+    src = ident.copy()
+    src[right] = ident[left]
+    src[left] = ident[right]
+    return src.astype(np.int32)
+
+
+def mirror_frames(x, mirror_src):
+    """x [..., D] float64 mirrored: joints exchanged, coordinate 0 negated."""
+    m = x.reshape(*x.shape[:-1], -1, 3)[..., np.asarray(mirror_src, dtype=np.int64), :].copy()
+    m[..., 0] = -m[..., 0]
+    return m.reshape(x.shape)
+
+
+def window_joint_weights(windows, dim_used):
+    """(joint_weight_all, joint_weight_use) of dataset/h36m.py:93-98 over
+    materialised windows [N][T][D], float64."""
+    n, t, d = windows.shape
+    x = windows.reshape(n, t, d // 3, 3)
+    motion = np.mean(np.abs(x[:, 1:] - x[:, :-1]), (0, 1, 3))
+    return _normalised_weights(motion, dim_used)
+
+
+def _check_dim_used(dim_used, D):
+    dim_used = np.asarray(dim_used, dtype=np.int64)
+    if (dim_used.ndim != 1 or not 1 <= len(dim_used) <= D or dim_used[0] < 0 or dim_used[-1] >= D
+            or np.any(np.diff(dim_used) <= 0)):
+        raise ValueError("dim_used: strictly increasing columns of D")
+    return dim_used
+
+
+def _normalised_weights(motion, dim_used):
+    with np.errstate(invalid="ignore", divide="ignore"):  # one joint, or none moving: NaN, as the reference
+        w_all = (motion - motion.min()) / (motion.max() - motion.min())
+    return w_all, w_all[np.unique(np.asarray(dim_used) // 3)]
+
+
+class MeanStd:
+    """The reference's MeanStdNorm interface (dataset/utils.py:2210-2236) for a
+    (mean, std) pair over the used dims: numpy in, numpy out; tensor in,
+    tensor out in the tensor's dtype and device (constants cached per both)."""
+
+    def __init__(self, mean, std):
+        self._mean = np.asarray(mean, dtype=np.float64).reshape(1, 1, -1)
+        self._std = np.asarray(std, dtype=np.float64).reshape(1, 1, -1)
+        self._cache = {}
+
+    def _ms(self, data):
+        if not isinstance(data, torch.Tensor):
+            return self._mean, self._std
+        key = (data.dtype, data.device)
+        if key not in self._cache:
+            # through fp32, as the reference's torch.Tensor(...) does
+            self._cache[key] = tuple(torch.from_numpy(a).float().to(data.dtype).to(data.device)
+                                     for a in (self._mean, self._std))
+        return self._cache[key]
+
+    def transform(self, data):
+        m, s = self._ms(data)
+        return (data - m) / s
+
+    def inverse(self, data):
+        m, s = self._ms(data)
+        return data * s + m
+
+
+def _as_scaler(scaler):
+    if scaler is None or (hasattr(scaler, "transform") and hasattr(scaler, "inverse")):
+        return scaler
+    mean, std = scaler
+    return MeanStd(mean, std)
+
+
+class DeviceSequences:
+    """A dataset resident on the device: frames [F][D], windows as start rows.
+
+    Build with ``from_windows``, ``from_sequences`` or ``from_dataset``.  The
+    reference dataset objects' attributes a runner reads are here:
+    ``joint_weight_use`` / ``joint_weight_all``, ``dim_used``, ``time_tsfm``
+    (None), ``scale_tsfm``; plus ``nbytes`` (device memory held) and ``len``
+    (windows, the mirrored ones included)."""
+
+    def __init__(self, frames, starts, seq_len, dim_used, input_n, output_n, padding, device, mirror_src=None,
+                 scale_tsfm=None, joint_weights=None):
+        frames = np.asarray(frames, dtype=np.float64)
+        starts = np.asarray(starts, dtype=np.int64)
+        if frames.ndim != 2 or frames.shape[0] < 1 or frames.shape[1] % 3 != 0:
+            raise ValueError(f"frames: expected [F][D] with D a multiple of 3, got {frames.shape}")
+        F, D = frames.shape
+        dim_used = _check_dim_used(dim_used, D)
+        T = int(seq_len)
+        if input_n + output_n != T or T < 1:
+            raise ValueError(f"input_n {input_n} + output_n {output_n} is not the window length {T}")
+        if starts.ndim != 1 or len(starts) < 1 or starts.min() < 0 or starts.max() + T > F:
+            raise ValueError(f"starts: windows of {T} frames outside the {F} stored frames")
+        if mirror_src is not None:
+            mirror_src = np.asarray(mirror_src, dtype=np.int32)
+            if mirror_src.shape != (D // 3,) or mirror_src.min() < 0 or mirror_src.max() >= D // 3:
+                raise ValueError("mirror_src: one source joint per joint")
+            if scale_tsfm is not None:
+                raise ValueError("a scaled set stores its mirrored frames (no on-the-fly mirror)")
+        self.device = torch.device(device)
+        self.seq_len, self.input_n, self.output_n, self.padding = T, int(input_n), int(output_n), bool(padding)
+        self.n_frames, self.n_dims, self.n_windows = F, D, len(starts)
+        self.dim_used = dim_used
+        self.time_tsfm = None
+        self.scale_tsfm = scale_tsfm
+        self.joint_weight_all, self.joint_weight_use = joint_weights if joint_weights is not None else (None, None)
+        fwd, inv = frame_maps(input_n, output_n, padding)
+        dev = self.device
+        self._frames = torch.from_numpy(frames.astype(np.float32)).to(dev)
+        self._used = None
+        if scale_tsfm is not None:
+            # (x - mean) / std in fp64 on the used columns, then the cast: what
+            # the reference's arrays hold when the engine casts a batch
+            used = np.asarray(scale_tsfm.transform(frames[None][:, :, dim_used]))[0]
+            self._used = torch.from_numpy(np.ascontiguousarray(used).astype(np.float32)).to(dev)
+        self._starts = torch.from_numpy(starts).to(dev)
+        self._dim_used = torch.from_numpy(dim_used.astype(np.int32)).to(dev)
+        self._frame_in, self._frame_inv = torch.from_numpy(fwd).to(dev), torch.from_numpy(inv).to(dev)
+        self._mirror_src = torch.from_numpy(mirror_src).to(dev) if mirror_src is not None else None
+        self._store = native.SeqStore(
+            frames=self._frames.data_ptr(), used=self._used.data_ptr() if self._used is not None else None,
+            starts=self._starts.data_ptr(), F=F, N=self.n_windows, T=T, D=D, Du=len(dim_used),
+            dim_used=self._dim_used.data_ptr(), frame_in=self._frame_in.data_ptr(),
+            frame_inv=self._frame_inv.data_ptr(),
+            mirror_src=self._mirror_src.data_ptr() if self._mirror_src is not None else None)
+
+    # ---- constructors ---------------------------------------------------------------
+    @classmethod
+    def from_windows(cls, all_seqs, dim_used, input_n, output_n, padding=True, device="cuda", mirror=None,
+                     scaler=None):
+        """Materialised windows [N][T][D] (what load_data_3d returns), stored
+        back to back.  mirror=(left, right) joint lists doubles the set as
+        get_mirror does; scaler: a MeanStdNorm-like object, (mean, std), or
+        True for the statistics of the used columns over every window frame
+        (dataset/h36m.py:81-85)."""
+        w = np.asarray(all_seqs, dtype=np.float64)
+        if w.ndim != 3 or w.shape[2] % 3 != 0 or w.shape[1] < 2:
+            raise ValueError(f"all_seqs: expected [N][T >= 2][D], D a multiple of 3, got {w.shape}")
+        dim_used = _check_dim_used(dim_used, w.shape[2])
+        mirror_src = mirror_source(w.shape[2] // 3, *mirror) if mirror is not None else None
+        full = w if mirror_src is None else np.concatenate((w, mirror_frames(w, mirror_src)), axis=0)
+        weights = window_joint_weights(full, dim_used)
+        if scaler is not None:  # mirror, then statistics, then scale -- on stored mirrored frames
+            w, mirror_src = full, None
+            if scaler is True:
+                u = w[:, :, np.asarray(dim_used)].reshape(w.shape[0] * w.shape[1], -1)
+                scaler = (np.mean(u, axis=0), np.std(u, axis=0))
+        n, t, d = w.shape
+        return cls(w.reshape(n * t, d), np.arange(n, dtype=np.int64) * t, t, dim_used, input_n, output_n, padding,
+                   device, mirror_src, _as_scaler(scaler), weights)
+
+    @classmethod
+    def from_sequences(cls, sequences, seq_len, dim_used, input_n, output_n, padding=True, device="cuda",
+                       mirror=None, scaler=None):
+        """Whole sequences [F_i][D]: every start 0..F_i - seq_len of every
+        sequence is a window (the training selection of load_data_3d,
+        dataset/utils.py:860-866), frames stored once.  The joint weights come
+        from how many windows hold each pair of consecutive frames."""
+        seqs = [np.asarray(s, dtype=np.float64) for s in sequences]
+        T = int(seq_len)
+        if not seqs or any(s.ndim != 2 or s.shape[1] != seqs[0].shape[1] or s.shape[0] < T for s in seqs) or T < 2:
+            raise ValueError(f"sequences: [F_i][D] arrays of at least seq_len = {T} >= 2 frames each")
+        D = seqs[0].shape[1]
+        if D % 3 != 0:
+            raise ValueError(f"sequences: D = {D} is not a multiple of 3")
+        dim_used = _check_dim_used(dim_used, D)
+        mirror_src = mirror_source(D // 3, *mirror) if mirror is not None else None
+        if scaler is True:
+            raise ValueError("from_sequences takes the scaler's statistics from the caller")
+        if scaler is not None and mirror_src is not None:
+            seqs = seqs + [mirror_frames(s, mirror_src) for s in seqs]
+        offsets = np.concatenate([[0], np.cumsum([len(s) for s in seqs])])
+        starts = np.concatenate([off + np.arange(len(s) - T + 1) for off, s in zip(offsets, seqs)])
+        # mean |x[t+1] - x[t]| over every window: pair p of a sequence lies in
+        # windows max(0, p - T + 2) .. min(p, F_i - T)
+        motion = np.zeros(D // 3)
+        for s in seqs:
+            p = np.arange(len(s) - 1)
+            mult = np.minimum(p, len(s) - T) - np.maximum(0, p - T + 2) + 1
+            motion += (np.abs(np.diff(s, axis=0)).reshape(len(p), -1, 3).sum(2) * mult[:, None]).sum(0)
+        if mirror_src is not None and scaler is None:  # the mirrored half moves joint j as mirror_src[j] moves
+            motion = (motion + motion[mirror_src]) / 2
+        motion /= len(starts) * (T - 1) * 3
+        if scaler is not None:
+            mirror_src = None
+        return cls(np.concatenate(seqs, axis=0), starts, T, dim_used, input_n, output_n, padding, device, mirror_src,
+                   _as_scaler(scaler), _normalised_weights(motion, dim_used))
+
+    @classmethod
+    def from_dataset(cls, ds, input_n, output_n, padding=True, device="cuda"):
+        """A reference dataset object (Human36M, CMUMocap, PW3D) as it is: its
+        all_seqs (mirrored windows already appended), dim_used, scale_tsfm and
+        joint weights."""
+        w = np.asarray(ds.all_seqs, dtype=np.float64)
+        n, t, d = w.shape
+        return cls(w.reshape(n * t, d), np.arange(n, dtype=np.int64) * t, t, ds.dim_used, input_n, output_n, padding,
+                   device, None, getattr(ds, "scale_tsfm", None), (ds.joint_weight_all, ds.joint_weight_use))
+
+    # ---- the set --------------------------------------------------------------------
+    def __len__(self):
+        return self.n_windows * (2 if self._mirror_src is not None else 1)
+
+    @property
+    def nbytes(self):
+        """Device memory the set holds."""
+        held = (self._frames, self._used, self._starts, self._dim_used, self._frame_in, self._frame_inv,
+                self._mirror_src)
+        return sum(t.numel() * t.element_size() for t in held if t is not None)
+
+    @property
+    def starts(self):
+        return self._starts
+
+    def gather(self, index, outputs=("inputs", "inputs_inv", "targets", "all_seqs"), out=None):
+        """(inputs, inputs_inv, targets, all_seqs) of the windows ``index``
+        (int64 device tensor [B]) by one dstd_batch_gather on the current
+        stream; a name missing from ``outputs`` is not produced (None).
+        ``out``: tensors to write into instead of fresh ones, by name."""
+        if self.device.type != "cuda":
+            raise RuntimeError(f"DeviceSequences.gather runs on the MI355X only (the set is on {self.device}); "
+                               "there is no CPU fallback")
+        if index.dtype != torch.int64 or index.device != self._frames.device or index.dim() != 1 \
+                or not index.is_contiguous():
+            raise ValueError("index: a contiguous int64 vector on the set's device")
+        B = index.numel()
+        shapes = {n: (B, self.seq_len, self.n_dims if n == "all_seqs" else len(self.dim_used))
+                  for n in ("inputs", "inputs_inv", "targets", "all_seqs")}
+        res = {}
+        for n in outputs:
+            t = out[n] if out is not None and n in out else torch.empty(shapes[n], dtype=torch.float32,
+                                                                        device=self._frames.device)
+            if tuple(t.shape) != shapes[n]:
+                raise ValueError(f"{n}: expected {shapes[n]}, got {tuple(t.shape)}")
+            res[n] = t
+        p = {n: native.ptr(t, n) for n, t in res.items()}
+        code = native.lib().dstd_batch_gather(ctypes.byref(self._store), index.data_ptr(), B, p.get("inputs"),
+                                              p.get("inputs_inv"), p.get("targets"), p.get("all_seqs"),
+                                              native.stream_handle(self._frames.device))
+        native.check(code, "dstd_batch_gather")
+        return tuple(res.get(n) for n in ("inputs", "inputs_inv", "targets", "all_seqs"))
+
+
+class DeviceLoader:
+    """Batches of a DeviceSequences in the reference loader's shape: iterating
+    yields ``(inputs, inputs_inv, targets, all_seqs)``, fp32 on the device,
+    one launch per batch and no host synchronisation.  Indices are generated
+    on the set's device; ``shuffle`` draws a permutation per epoch from a
+    device generator seeded ``seed + epoch`` (epochs counted per iteration
+    started).  ``last_index`` is the index tensor of the batch just yielded."""
+
+    def __init__(self, seqs, batch_size, shuffle=False, drop_last=False, seed=0):
+        if batch_size < 1:
+            raise ValueError(f"batch_size {batch_size}")
+        self.seqs, self.batch_size = seqs, int(batch_size)
+        self.shuffle, self.drop_last, self.seed = bool(shuffle), bool(drop_last), int(seed)
+        self.epoch = 0
+        self.last_index = None
+        self._order = None
+        self._generator = None
+
+    def __len__(self):
+        n = len(self.seqs)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def index_batches(self):
+        """The epoch's index tensors, one per batch (what ``__iter__`` gathers)."""
+        n, dev = len(self.seqs), self.seqs.device
+        if self.shuffle:
+            if self._generator is None:
+                self._generator = torch.Generator(device=dev)
+            self._generator.manual_seed(self.seed + self.epoch)
+            order = torch.randperm(n, generator=self._generator, device=dev)
+        else:
+            if self._order is None:
+                self._order = torch.arange(n, dtype=torch.int64, device=dev)
+            order = self._order
+        self.epoch += 1
+        for i in range(len(self)):
+            yield order[i * self.batch_size:(i + 1) * self.batch_size]
+
+    def __iter__(self):
+        for idx in self.index_batches():
+            self.last_index = idx
+            yield self.seqs.gather(idx)
+
+
+__all__ = ["DeviceSequences", "DeviceLoader", "MeanStd", "frame_maps", "mirror_source"]

@@ -105,6 +105,15 @@ class LossProblem(ctypes.Structure):
                 ("V", ctypes.c_int), ("targ_T", ctypes.c_int), ("targ_t0", ctypes.c_int), ("targ_step", ctypes.c_int)]
 
 
+class SeqStore(ctypes.Structure):
+    """include/dstd_gcn_data.h dstd_seq_store: frames [F][D] resident on the
+    device, windows as start rows, and the tables a batch is gathered through."""
+    _fields_ = [("frames", ctypes.c_void_p), ("used", ctypes.c_void_p), ("starts", ctypes.c_void_p),
+                ("F", ctypes.c_longlong), ("N", ctypes.c_longlong), ("T", ctypes.c_int), ("D", ctypes.c_int),
+                ("Du", ctypes.c_int), ("dim_used", ctypes.c_void_p), ("frame_in", ctypes.c_void_p),
+                ("frame_inv", ctypes.c_void_p), ("mirror_src", ctypes.c_void_p)]
+
+
 # include/dstd_gcn_loss.h DSTD_LOSS_*: term bits, slot k of a values / coef row is bit 1 << k
 LOSS_JL2, LOSS_TL2, LOSS_CL1, LOSS_CL2 = 1, 2, 4, 8
 LOSS_NTERMS = 4
@@ -299,6 +308,11 @@ def lib():
             L.dstd_model_fwd_taps.restype = ci
             L.dstd_model_fwd_taps.argtypes = [ctypes.POINTER(ModelParams), vp, ci, vp, ctypes.POINTER(BlockTaps), vp,
                                               sz, vp, uf]
+        # device-resident dataset (include/dstd_gcn_data.h; absent from an
+        # earlier revision's library loaded for an A/B)
+        if hasattr(L, "dstd_batch_gather"):
+            L.dstd_batch_gather.restype = ci
+            L.dstd_batch_gather.argtypes = [ctypes.POINTER(SeqStore), vp, ci, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -322,6 +336,7 @@ AUX_EXPORTS = ("dstd_ctg_workspace_bytes", "dstd_ctg_fwd", "dstd_ctg_bwd", "dstd
 LOSS_EXPORTS = ("dstd_losses_workspace_bytes", "dstd_losses_fwd", "dstd_losses_bwd")
 TAPS_EXPORTS = ("dstd_block_taps_workspace_bytes", "dstd_model_taps_workspace_bytes", "dstd_block_fwd_taps",
                 "dstd_model_fwd_taps")
+DATA_EXPORTS = ("dstd_batch_gather",)
 
 
 ARITHMETICS = ("split", "fp32")
