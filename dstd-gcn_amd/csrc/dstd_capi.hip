@@ -11,6 +11,7 @@
 #include "../../include/dstd_gcn_taps.h"
 #include "dstd_common.h"
 #include "dstd_hilo.h"
+#include "dstd_host.h"
 #include "dstd_kernels.h"
 #include "dstd_plan.h"
 #include "dstd_taps.h"
@@ -18,29 +19,6 @@
 using namespace dstd;
 
 namespace {
-
-constexpr int kMaxT = 128;  // the generic kernels cover T <= 128 (adjacency row groups past 112)
-constexpr int kMaxV = 32;
-constexpr int kMaxC = 64;
-
-// Bump allocator over the caller's workspace.  With base == nullptr it only
-// measures, so *_workspace_bytes and the forward share one layout.
-struct Carver {
-  char* base;
-  size_t off = 0;
-  float* take(size_t nfloats) {
-    off = (off + 255) & ~size_t(255);
-    float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
-    off += nfloats * sizeof(float);
-    return p;
-  }
-};
-
-#define DSTD_TRY(expr)                         \
-  do {                                         \
-    hipError_t _e = (expr);                    \
-    if (_e != hipSuccess) return (int)_e;      \
-  } while (0)
 
 bool shape_ok(int B, int T, int V) { return B > 0 && T > 1 && V > 0; }
 bool limits_ok(int T, int V, int cin, int cout) {
@@ -54,18 +32,6 @@ int model_shape_code(int B, int T, int V, int C, int layers) {
 constexpr unsigned kModelFwdFlags = DSTD_FWD_REUSE_CONSTANTS | DSTD_FWD_EXACT_FP32 | DSTD_FWD_SEPARATE_ADJ |
                                     DSTD_FWD_FUSED_TEMPORAL | DSTD_FWD_SEPARATE_BLOCK | DSTD_FWD_SEPARATE_ENCODERS |
                                     DSTD_FWD_SEPARATE_ENDS;
-bool gc_ok(const dstd_gc_weights* w) {
-  return w && w->wf && w->bf && w->wm1 && w->bm1 && w->wm2 && w->bm2 && w->wrm && w->brm;
-}
-bool bn_ok(const dstd_bn& b) { return b.weight && b.bias && b.running_mean && b.running_var; }
-bool block_ok(const dstd_block_params* p) {
-  if (!p || !p->A_s || !p->W_s || !p->R_s || !p->A_t || !p->R_t || !p->alpha_sm || !p->alpha_tm || !p->prelu)
-    return false;
-  if (!gc_ok(&p->conv_s[0]) || !gc_ok(&p->conv_s[1]) || !gc_ok(&p->conv_t) || !bn_ok(p->bn)) return false;
-  if (p->cin != p->cout && (!p->res_w || !p->res_b || !bn_ok(p->res_bn))) return false;
-  return true;
-}
-
 // Optional per-launch event brackets (dstd_model_fwd_profiled).
 struct Prof {
   dstd_profile* p = nullptr;
@@ -905,7 +871,7 @@ namespace {
 int block_fwd(const dstd_block_params* p, const float* x, int B, int T, int V, float* y, void* workspace,
               size_t workspace_bytes, void* stream, unsigned flags, const dstd_block_taps* taps) {
   StreamDeviceGuard dev_guard_(stream, x);
-  if (!x || !y || !workspace || !block_ok(p) || !shape_ok(B, T, V)) return DSTD_EINVAL;
+  if (!x || !y || !workspace || !block_ptrs_ok(p) || !shape_ok(B, T, V)) return DSTD_EINVAL;
   if (!limits_ok(T, V, p->cin, p->cout)) return DSTD_ELIMIT;
   if (workspace_bytes < dstd_block_workspace_bytes(B, p->cin, p->cout, T, V)) return DSTD_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
@@ -992,10 +958,10 @@ int model_fwd(const dstd_model_params* p, const float* x, int B, float* y, void*
   const int T = p->T, V = p->V, C = p->num_feature, L_ = p->num_layers, NB = L_ + 2;
   if (p->in_channels != 6) return DSTD_EINVAL;
   if (const int e = model_shape_code(B, T, V, C, L_)) return e;
-  if (!block_ok(&p->st_in) || !block_ok(&p->st_out) || !bn_ok(p->bn_in) || !p->prelu) return DSTD_EINVAL;
+  if (!block_ptrs_ok(&p->st_in) || !block_ptrs_ok(&p->st_out) || !bn_ok(p->bn_in) || !p->prelu) return DSTD_EINVAL;
   if (p->st_in.cin != 6 || p->st_in.cout != C || p->st_out.cin != C || p->st_out.cout != 3) return DSTD_EINVAL;
   for (int i = 0; i < L_; ++i) {
-    if (!block_ok(&p->enc[i]) || !bn_ok(p->enc_bn[i]) || !p->enc_prelu[i]) return DSTD_EINVAL;
+    if (!block_ptrs_ok(&p->enc[i]) || !bn_ok(p->enc_bn[i]) || !p->enc_prelu[i]) return DSTD_EINVAL;
     if (p->enc[i].cin != C || p->enc[i].cout != C) return DSTD_EINVAL;
   }
   if (workspace_bytes < dstd_model_workspace_bytes(B, T, V, C, L_)) return DSTD_EWORKSPACE;

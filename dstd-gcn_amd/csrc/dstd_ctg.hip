@@ -8,28 +8,13 @@
 #include "../../include/dstd_gcn.h"
 #include "../../include/dstd_gcn_aux.h"
 #include "dstd_common.h"
+#include "dstd_host.h"
 #include "dstd_train.h"
 
+using dstd::Carver;
 using namespace dstd::train;
 
 namespace {
-
-struct Carver {
-  char* base;
-  size_t off = 0;
-  float* take(size_t nfloats) {
-    off = (off + 255) & ~size_t(255);
-    float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
-    off += nfloats * sizeof(float);
-    return p;
-  }
-};
-
-#define DSTD_TRY(expr)                    \
-  do {                                    \
-    hipError_t _e = (expr);               \
-    if (_e != hipSuccess) return (int)_e; \
-  } while (0)
 
 struct CtgWs {
   float *x1, *dx1, *gs;

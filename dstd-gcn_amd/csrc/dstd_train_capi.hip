@@ -19,71 +19,38 @@
 
 #include "../../include/dstd_gcn_train.h"
 #include "dstd_common.h"
+#include "dstd_host.h"
 #include "dstd_train.h"
 
+using namespace dstd;
 using namespace dstd::train;
 
 namespace {
 
-constexpr int kMaxT = 128;  // same envelope as the forward (dstd_capi.hip)
-constexpr int kMaxV = 32;
-constexpr int kMaxC = 64;
-constexpr int kMaxRed = 8;  // red_channels of one DSTDGC (P / Q channels each)
 constexpr unsigned kTrainFlags = DSTD_TRAIN_RUNNING_STATS | DSTD_TRAIN_PAIRED;
 constexpr unsigned kModelTrainFlags = kTrainFlags | DSTD_TRAIN_SEED_DEVICE | DSTD_TRAIN_ONE_STREAM;
 
-struct Carver {
-  char* base;
-  size_t off = 0;
-  float* take(size_t nfloats) {
-    off = (off + 255) & ~size_t(255);
-    float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
-    off += nfloats * sizeof(float);
-    return p;
-  }
-};
-
-#define DSTD_TRY(expr)                    \
-  do {                                    \
-    hipError_t _e = (expr);               \
-    if (_e != hipSuccess) return (int)_e; \
-  } while (0)
-
-#define DSTD_TRYH(expr)                  \
-  do {                                   \
-    hipError_t _e = (expr);              \
-    if (_e != hipSuccess) return _e;     \
-  } while (0)
-
 bool shape_ok(int B, int T, int V) { return B > 0 && T > 1 && V > 0 && T <= kMaxT && V <= kMaxV; }
 bool ch_ok(int c) { return c >= 1 && c <= kMaxC; }
-bool gc_ok(const dstd_gc_weights* w) {
-  return w && w->wf && w->bf && w->wm1 && w->bm1 && w->wm2 && w->bm2 && w->wrm && w->brm;
-}
-bool gg_ok(const dstd_gc_grads* g) {
-  return g && g->wf && g->bf && g->wm1 && g->bm1 && g->wm2 && g->bm2 && g->wrm && g->brm;
-}
-bool bn_ok(const dstd_bn& b) { return b.weight && b.bias && b.running_mean && b.running_var; }
-bool bng_ok(const dstd_bn_grads& b) { return b.weight && b.bias; }
-bool block_ok(const dstd_block_params* p) {
-  if (!p || !p->A_s || !p->W_s || !p->R_s || !p->A_t || !p->R_t || !p->alpha_sm || !p->alpha_tm || !p->prelu)
-    return false;
-  if (!ch_ok(p->cin) || !ch_ok(p->cout)) return false;
-  if (!gc_ok(&p->conv_s[0]) || !gc_ok(&p->conv_s[1]) || !gc_ok(&p->conv_t) || !bn_ok(p->bn)) return false;
-  if (p->cin != p->cout && (!p->res_w || !p->res_b || !bn_ok(p->res_bn))) return false;
-  return true;
-}
+// The training path judges a block's channel counts together with its
+// pointers, as an argument error: cout = 65 is DSTD_EINVAL here and DSTD_ELIMIT
+// in the eval forward (whose limits_ok answers).  Pinned by
+// tests/test_gpu_envelope.py OUTSIDE_BLOCK; kept apart from block_ptrs_ok so
+// that the difference stays visible where it is made.
+bool block_channels_ok(const dstd_block_params* p) { return ch_ok(p->cin) && ch_ok(p->cout); }
 bool block_grads_ok(const dstd_block_params* p, const dstd_block_grads* g) {
-  if (!g || !g->W_s || !g->R_s || !g->R_t || !g->alpha_sm || !g->alpha_tm || !g->prelu) return false;
+  if (!p || !g || !g->W_s || !g->R_s || !g->R_t || !g->alpha_sm || !g->alpha_tm || !g->prelu) return false;
   if (!gg_ok(&g->conv_s[0]) || !gg_ok(&g->conv_s[1]) || !gg_ok(&g->conv_t) || !bng_ok(g->bn)) return false;
   if (p->cin != p->cout && (!g->res_w || !g->res_b || !bng_ok(g->res_bn))) return false;
   return true;
 }
 bool model_ok(const dstd_model_params* p) {
+  // pointers, then (training path only) the channel range: block_channels_ok
+  auto blk_ok = [](const dstd_block_params* b) { return block_ptrs_ok(b) && block_channels_ok(b); };
   if (!p || p->num_layers < 0 || p->num_layers > DSTD_MAX_LAYERS || p->in_channels != 6) return false;
-  if (!block_ok(&p->st_in) || !bn_ok(p->bn_in) || !p->prelu || !block_ok(&p->st_out)) return false;
+  if (!blk_ok(&p->st_in) || !bn_ok(p->bn_in) || !p->prelu || !blk_ok(&p->st_out)) return false;
   for (int i = 0; i < p->num_layers; ++i)
-    if (!block_ok(&p->enc[i]) || !bn_ok(p->enc_bn[i]) || !p->enc_prelu[i]) return false;
+    if (!blk_ok(&p->enc[i]) || !bn_ok(p->enc_bn[i]) || !p->enc_prelu[i]) return false;
   return true;
 }
 
@@ -207,9 +174,8 @@ void wgrad_release(WgradRes* r) {
 
 // One backward's use of the weight-gradient stream (null res: one stream).
 struct Wgrad {
-  WgradRes* res = nullptr;
-  Wgrad() = default;
-  explicit Wgrad(WgradRes* r) : res(r) {}
+  WgradRes* res;
+  explicit Wgrad(hipStream_t caller, WgradRes* r = nullptr) : res(r), main(caller) {}
   // an error return between a fork and the success-path join() must not
   // leave side-stream work unordered before the caller's stream (it still
   // reads the workspace / saved state and writes the gradient arena), nor a
@@ -220,7 +186,7 @@ struct Wgrad {
   }
   Wgrad(const Wgrad&) = delete;
   Wgrad& operator=(const Wgrad&) = delete;
-  hipStream_t main = nullptr;
+  hipStream_t main;  // the caller's stream
   int next = 0;
   bool used[2] = {false, false};
   bool any = false;
@@ -254,6 +220,20 @@ struct Wgrad {
     return hipStreamWaitEvent(main, res->join, 0);
   }
 };
+// What one training call carries to every level below its entry point.  wg
+// is never null: a call without a second stream (the op and block entry
+// points, DSTD_TRAIN_ONE_STREAM) carries a Wgrad with no WgradRes.
+struct TrainCall {
+  int B, T, V;
+  float momentum;  // of the forward's running-statistics update
+  unsigned flags;  // DSTD_TRAIN_*
+  const dstd_bn_sync* sync;
+  hipStream_t s;  // the caller's stream
+  Wgrad* wg;
+  int use_running() const { return (flags & DSTD_TRAIN_RUNNING_STATS) != 0; }
+  int groups() const { return (flags & DSTD_TRAIN_PAIRED) ? 2 : 1; }
+};
+
 // Reduction / BatchNorm / adjacency-backward scratch for a geometry.
 size_t red_floats(const OpGeom& g) {
   return std::max(std::max(reduce_scratch_floats(std::max(std::max(g.NN2, g.CG()), std::max(g.A, g.cin))),
@@ -382,18 +362,26 @@ hipError_t op_fwd(const OpGeom& g, const float* x, const dstd_gc_weights* w, con
   return op_fwd_agg(g, y, beta_y, sv, s);
 }
 
-// dx_beta 0: dx (=) instead of (+=); assign_dA: dA likewise (block-internal
-// buffers; the op entry point accumulates both)
+// Where one op's adjacency gradients go: dA ([NN][NN]) and dalpha ([1])
+// accumulate, or dA is assigned (assign_dA); dW2 / Amul (optional): also
+// dW2 += dA * Amul (the spatial adjacency's dW_s = dA * A_s, adj_bwd_finish).
+struct AdjGrads {
+  float* dA;
+  float* dalpha;
+  float* dW2 = nullptr;
+  const float* Amul = nullptr;
+  int assign_dA = 0;
+};
+// dx (may be null) = dx_beta * dx + the op's input gradient: 1 accumulates
+// (the entry point's contract), 0 assigns (block-internal buffers).
 hipError_t op_bwd(const OpGeom& g, const float* x, const dstd_gc_weights* w, const float* alpha, const OpSaved& sv,
-                  const float* dy, float* dx, const dstd_gc_grads* gr, float* dA, float* dalpha, const OpWs& ws0,
-                  hipStream_t s, float dx_beta = 1.f, int assign_dA = 0, Wgrad* wg = nullptr,
-                  float* dW2 = nullptr, const float* Amul = nullptr) {
+                  const float* dy, float* dx, float dx_beta, const dstd_gc_grads* gr, const AdjGrads& ag,
+                  const OpWs& ws0, const TrainCall& c) {
   const long long ldG = (long long)g.CG() * g.TV;
   OpWs ws = ws0;
   int slot = 0;
-  Wgrad none;
-  if (!wg) wg = &none;
-  wg->main = s;
+  const hipStream_t s = c.s;
+  Wgrad* const wg = c.wg;
   DSTD_TRYH(wg->take(ws0, ws.dG, ws.dD, slot));
   // the weight-gradient reductions' stream and scratch
   const hipStream_t ws_s = wg->res ? wg->res->st : s;
@@ -432,7 +420,8 @@ hipError_t op_bwd(const OpGeom& g, const float* x, const dstd_gc_weights* w, con
   float* const adjs = wg->res ? ws0.adjp[slot] : ws.red;
   DSTD_TRYH(adj_bwd_part(ws.dD, sv.E, alpha, g.B, g.A, g.NN2, adjs, s, ws.dDp, nparts));
   const bool fset = wg->res != nullptr;
-  if (!fset) DSTD_TRYH(adj_bwd_finish(g.B, g.A, g.NN2, dA, gr->brm, dalpha, adjs, s, assign_dA, dW2, Amul));
+  if (!fset)
+    DSTD_TRYH(adj_bwd_finish(g.B, g.A, g.NN2, ag.dA, gr->brm, ag.dalpha, adjs, s, ag.assign_dA, ag.dW2, ag.Amul));
   if (wg->res) DSTD_TRYH(wg->fork());
   GemmFinish wrf, gwf;
   const float* dE = ws.dD;
@@ -464,7 +453,8 @@ hipError_t op_bwd(const OpGeom& g, const float* x, const dstd_gc_weights* w, con
   if (wg->res) {  // queued before dx, which then runs beside it
     DSTD_TRYH(wg->fork());
     DSTD_TRYH(gemm(gw, ws_gs, ws_s, &gwf));
-    DSTD_TRYH(finish_set(g.B, g.A, g.NN2, dA, gr->brm, dalpha, adjs, assign_dA, dW2, Amul, &wrf, &gwf, ws_s));
+    DSTD_TRYH(finish_set(g.B, g.A, g.NN2, ag.dA, gr->brm, ag.dalpha, adjs, ag.assign_dA, ag.dW2, ag.Amul, &wrf, &gwf,
+                         ws_s));
     DSTD_TRYH(wg->release(slot));
   }
   // the three 1x1 convs at once: dx += Wp^T dG;  [dWp | dbp] = sum dG [x; 1]^T
@@ -539,16 +529,80 @@ void pack_block(CopyJobs& js, const dstd_block_params* p, const BlockSaved& S, i
   pack_jobs(js, &p->conv_t, S.op[2], gt);
 }
 
+// ---------------------------------------------------------------------------
+// BatchNorm sites.  One value describes a BatchNorm (+ PReLU) of the model:
+// its parameters, what it reads and writes, and the tensors it saves for its
+// backward.  The forward's BnFwd and the backward's BnBwd are both built from
+// it (bn_fwd / bn_bwd), so the two directions cannot name different tensors;
+// the call's flags and sync reach both through the TrainCall.
+// ---------------------------------------------------------------------------
+struct BnSite {
+  const dstd_bn* bn;
+  const float* prelu;  // the PReLU slope behind the BN (null: none)
+  int C;
+  const float* x;
+  const float* x2;   // optional pre-add (the encoders' identity residual)
+  const float* res;  // optional post-add (the block's residual branch)
+  float* out;
+  float *zsave, *mean, *rstd;  // saved: z (with a PReLU only), statistics per BN group
+};
+BnFwd bn_fwd(const BnSite& b, const TrainCall& c) {
+  BnFwd a;
+  a.x = b.x, a.x2 = b.x2, a.res = b.res;
+  a.gamma = b.bn->weight, a.beta = b.bn->bias;
+  a.running_mean = const_cast<float*>(b.bn->running_mean);
+  a.running_var = const_cast<float*>(b.bn->running_var);
+  a.momentum = c.momentum, a.eps = b.bn->eps;
+  a.prelu = b.prelu;
+  a.out = b.out, a.zsave = b.zsave, a.mean = b.mean, a.rstd = b.rstd;
+  a.use_running = c.use_running(), a.groups = c.groups(), a.sync = c.sync;
+  return a;
+}
+// Where a site's backward writes: du = d(x) (=), dz_out (optional) = dz
+// (+ dz_add), and the accumulated parameter gradients.
+struct BnSiteGrads {
+  float* du;
+  const dstd_bn_grads* g;
+  float* dprelu = nullptr;
+  float* dz_out = nullptr;
+  const float* dz_add = nullptr;
+};
+BnBwd bn_bwd(const BnSite& b, const TrainCall& c, const float* dout, const BnSiteGrads& d) {
+  BnBwd a;
+  a.x = b.x, a.x2 = b.x2, a.zsave = b.zsave, a.prelu = b.prelu;
+  a.dout = dout;
+  a.mean = b.mean, a.rstd = b.rstd, a.gamma = b.bn->weight;
+  a.du = d.du, a.dz_out = d.dz_out, a.dz_add = d.dz_add;
+  a.dgamma = d.g->weight, a.dbeta = d.g->bias;
+  a.use_running = c.use_running(), a.groups = c.groups(), a.sync = c.sync;
+  return a;
+}
+hipError_t site_fwd(const BnSite& b, const TrainCall& c, float* scratch) {
+  return bn_train_fwd(bn_fwd(b, c), c.B, b.C, c.T, c.V, scratch, c.s);
+}
+hipError_t site_bwd(const BnSite& b, const TrainCall& c, const float* dout, const BnSiteGrads& d, float* scratch) {
+  return bn_train_bwd(bn_bwd(b, c, dout, d), c.B, b.C, c.T, c.V, scratch, d.dprelu, c.s);
+}
+// The block's two sites: the residual branch's BN(conv1x1(x)) (:117-121,
+// cin != cout only) and h = PReLU(BN(ysp) + r) (:151-154).
+BnSite block_res_site(const dstd_block_params* p, const BlockSaved& S) {
+  return BnSite{&p->res_bn, nullptr, p->cout, S.rc, nullptr, nullptr, S.r, nullptr, S.rmean, S.rrstd};
+}
+BnSite block_main_site(const dstd_block_params* p, const BlockSaved& S, const float* r) {
+  return BnSite{&p->bn, p->prelu, p->cout, S.ysp, nullptr, r, S.h, S.z, S.mean, S.rstd};
+}
+
 // packed: the caller already packed the block's weights (the model forward
 // packs all blocks in two launches)
-// side (optional): a second stream of the device (the backward's weight-
-// gradient stream set): the second spatial op builds its adjacency there while
-// the first runs on s; its aggregation then adds into y on s after the
-// first's, so the result is bit-identical to the one-stream order.
-hipError_t block_fwd(const dstd_block_params* p, const float* x, int B, int T, int V, float momentum, float* y,
-                     const BlockSaved& S, hipStream_t s, int run = 0, const dstd_bn_sync* sync = nullptr,
-                     bool packed = false, Wgrad* side = nullptr) {
-  const int cin = p->cin, cout = p->cout, TV = T * V;
+// With a second stream (c.wg->res: the backward's weight-gradient stream set)
+// the second spatial op builds its adjacency there while the first runs on
+// c.s; its aggregation then adds into y on c.s after the first's, so the
+// result is bit-identical to the one-stream order.
+hipError_t block_fwd(const dstd_block_params* p, const float* x, float* y, const BlockSaved& S, bool packed,
+                     const TrainCall& c) {
+  const int B = c.B, T = c.T, V = c.V, cin = p->cin, cout = p->cout, TV = T * V;
+  const hipStream_t s = c.s;
+  Wgrad* const side = c.wg;
   const bool res = cin != cout;
   const OpGeom gs(DSTD_MODE_SPATIAL, B, cin, cout, T, V);
   const OpGeom gt(DSTD_MODE_TEMPORAL, B, cout, cout, T, V);
@@ -558,8 +612,7 @@ hipError_t block_fwd(const dstd_block_params* p, const float* x, int B, int T, i
     DSTD_TRYH(copy_jobs(js, s));
   }
   // :145-150, A_s*W_s + R_s (:146-149)
-  if (side && side->res) {
-    side->main = s;
+  if (side->res) {
     DSTD_TRYH(side->fork());
     DSTD_TRYH(op_fwd_adj(gs, x, &p->conv_s[1], p->A_s + V * V, p->W_s + V * V, p->R_s + V * V, p->alpha_sm, S.op[1],
                          side->res->st));
@@ -571,98 +624,36 @@ hipError_t block_fwd(const dstd_block_params* p, const float* x, int B, int T, i
       DSTD_TRYH(op_fwd(gs, x, &p->conv_s[i], p->A_s + i * V * V, p->W_s + i * V * V, p->R_s + i * V * V,
                        p->alpha_sm, S.ysp, i ? 1.f : 0.f, S.op[i], s));
   }
-  const float* r = x;
   if (res) {  // residual Conv1x1 + BatchNorm (:117-121)
     DSTD_TRYH(gemm(conv_fwd(p->res_w, p->res_b, x, S.rc, B, cin, cout, TV), nullptr, s));
-    BnFwd rb;
-    rb.x = S.rc;
-    rb.gamma = p->res_bn.weight;
-    rb.beta = p->res_bn.bias;
-    rb.running_mean = const_cast<float*>(p->res_bn.running_mean);
-    rb.running_var = const_cast<float*>(p->res_bn.running_var);
-    rb.momentum = momentum;
-    rb.eps = p->res_bn.eps;
-    rb.out = S.r;
-    rb.mean = S.rmean;
-    rb.rstd = S.rrstd;
-    rb.use_running = (run & DSTD_TRAIN_RUNNING_STATS) != 0;
-    rb.groups = (run & DSTD_TRAIN_PAIRED) ? 2 : 1;
-    rb.sync = sync;
-    DSTD_TRYH(bn_train_fwd(rb, B, cout, T, V, S.red, s));
-    r = S.r;
+    DSTD_TRYH(site_fwd(block_res_site(p, S), c, S.red));
   }
-  BnFwd bb;  // h = PReLU(BN(y) + r)  (:151-154)
-  bb.x = S.ysp;
-  bb.res = r;
-  bb.gamma = p->bn.weight;
-  bb.beta = p->bn.bias;
-  bb.running_mean = const_cast<float*>(p->bn.running_mean);
-  bb.running_var = const_cast<float*>(p->bn.running_var);
-  bb.momentum = momentum;
-  bb.eps = p->bn.eps;
-  bb.prelu = p->prelu;
-  bb.out = S.h;
-  bb.zsave = S.z;
-  bb.mean = S.mean;
-  bb.rstd = S.rstd;
-  bb.use_running = (run & DSTD_TRAIN_RUNNING_STATS) != 0;
-  bb.groups = (run & DSTD_TRAIN_PAIRED) ? 2 : 1;
-  bb.sync = sync;
-  DSTD_TRYH(bn_train_fwd(bb, B, cout, T, V, S.red, s));
+  DSTD_TRYH(site_fwd(block_main_site(p, S, res ? S.r : x), c, S.red));  // h = PReLU(BN(y) + r)  (:151-154)
   return op_fwd(gt, S.h, &p->conv_t, p->A_t, nullptr, p->R_t, p->alpha_tm, y, 0.f, S.op[2], s);  // :156-162
 }
 
 // dx_init: dx holds nothing yet -- the first contribution assigns (no
 // memset); dx_extra (no residual conv only): also added to dx (the
 // encoders' identity path of the model backward).
-hipError_t block_bwd(const dstd_block_params* p, const float* x, int B, int T, int V, const BlockSaved& S,
-                     const float* dy, float* dx, const dstd_block_grads* g, const BlockWs& W, hipStream_t s,
-                     int run = 0, bool dx_init = false, const float* dx_extra = nullptr,
-                     const dstd_bn_sync* sync = nullptr, Wgrad* wg = nullptr) {
-  const int cin = p->cin, cout = p->cout, TV = T * V;
+hipError_t block_bwd(const dstd_block_params* p, const float* x, const BlockSaved& S, const float* dy, float* dx,
+                     bool dx_init, const float* dx_extra, const dstd_block_grads* g, const BlockWs& W,
+                     const TrainCall& c) {
+  const int B = c.B, T = c.T, V = c.V, cin = p->cin, cout = p->cout, TV = T * V;
+  const hipStream_t s = c.s;
   const bool res = cin != cout;
   const size_t act = (size_t)B * cout * TV;
   const OpGeom gt(DSTD_MODE_TEMPORAL, B, cout, cout, T, V);
   // A_t + R_t: dR_t = dA; dh (=) the temporal op's input gradient
-  DSTD_TRYH(op_bwd(gt, S.h, &p->conv_t, p->alpha_tm, S.op[2], dy, W.dh, &g->conv_t, g->R_t, g->alpha_tm, W.op, s,
-                   0.f, 0, wg));
-  BnBwd bb;
-  bb.x = S.ysp;
-  bb.zsave = S.z;
-  bb.prelu = p->prelu;
-  bb.dout = W.dh;
-  bb.mean = S.mean;
-  bb.rstd = S.rstd;
-  bb.gamma = p->bn.weight;
-  bb.du = W.dysp;
-  bb.dz_out = W.dr;
+  DSTD_TRYH(op_bwd(gt, S.h, &p->conv_t, p->alpha_tm, S.op[2], dy, W.dh, 0.f, &g->conv_t, AdjGrads{g->R_t, g->alpha_tm},
+                   W.op, c));
+  BnSiteGrads mg{W.dysp, &g->bn, g->prelu, W.dr};
   // identity residual, first contribution to dx: the BN backward writes
   // dx = dz (+ dx_extra) itself (no separate accumulate pass)
   const bool dz_to_dx = !res && dx && dx_init;
-  if (dz_to_dx) {
-    bb.dz_out = dx;
-    bb.dz_add = dx_extra;
-  }
-  bb.dgamma = g->bn.weight;
-  bb.dbeta = g->bn.bias;
-  bb.use_running = (run & DSTD_TRAIN_RUNNING_STATS) != 0;
-  bb.groups = (run & DSTD_TRAIN_PAIRED) ? 2 : 1;
-  bb.sync = sync;
-  DSTD_TRYH(bn_train_bwd(bb, B, cout, T, V, W.op.red, g->prelu, s));
+  if (dz_to_dx) mg.dz_out = dx, mg.dz_add = dx_extra;
+  DSTD_TRYH(site_bwd(block_main_site(p, S, res ? S.r : x), c, W.dh, mg, W.op.red));
   if (res) {
-    BnBwd rb;
-    rb.x = S.rc;
-    rb.dout = W.dr;
-    rb.mean = S.rmean;
-    rb.rstd = S.rrstd;
-    rb.gamma = p->res_bn.weight;
-    rb.du = W.drc;
-    rb.dgamma = g->res_bn.weight;
-    rb.dbeta = g->res_bn.bias;
-    rb.use_running = (run & DSTD_TRAIN_RUNNING_STATS) != 0;
-    rb.groups = (run & DSTD_TRAIN_PAIRED) ? 2 : 1;
-    rb.sync = sync;
-    DSTD_TRYH(bn_train_bwd(rb, B, cout, T, V, W.op.red, nullptr, s));
+    DSTD_TRYH(site_bwd(block_res_site(p, S), c, W.dr, BnSiteGrads{W.drc, &g->res_bn}, W.op.red));
     if (dx_extra) return hipErrorInvalidValue;
     DSTD_TRYH(conv_bwd(p->res_w, x, W.drc, dx, g->res_w, g->res_b, B, cin, cout, TV, W.op.gs, s,
                        dx_init ? 0.f : 1.f));
@@ -673,18 +664,24 @@ hipError_t block_bwd(const dstd_block_params* p, const float* x, int B, int T, i
   // A_s*W_s + R_s with A_s constant: each graph's dA accumulates straight into
   // its dR_s, and dW_s += dA * A_s, in the adjacency-backward finish
   for (int i = 0; i < 2; ++i)
-    DSTD_TRYH(op_bwd(gs, x, &p->conv_s[i], p->alpha_sm, S.op[i], W.dysp, dx, &g->conv_s[i], g->R_s + i * V * V,
-                     g->alpha_sm, W.op, s, 1.f, 0, wg, g->W_s + i * V * V, p->A_s + i * V * V));
+    DSTD_TRYH(op_bwd(gs, x, &p->conv_s[i], p->alpha_sm, S.op[i], W.dysp, dx, 1.f, &g->conv_s[i],
+                     AdjGrads{g->R_s + i * V * V, g->alpha_sm, g->W_s + i * V * V, p->A_s + i * V * V}, W.op, c));
   return hipSuccess;
 }
 
 // ---------------------------------------------------------------------------
 // whole DSTDGCN
 // ---------------------------------------------------------------------------
+// The saved tensors of a BatchNorm site between two blocks (bn_in and every
+// enc_bn[i]): the block output it reads, z and the statistics per BN group.
+struct SiteSaved {
+  float *y, *z, *mean, *rstd;
+};
 struct ModelSaved {
-  float *X0, *y0, *z0, *hp0, *m0, *r0, *o;
+  float *X0, *o;
+  SiteSaved in, enc_bn[DSTD_MAX_LAYERS];
+  float* hp0;  // bn_in's output before the dropout (dropout_p > 0 only)
   float* h[DSTD_MAX_LAYERS + 1];
-  float *yb[DSTD_MAX_LAYERS], *ze[DSTD_MAX_LAYERS], *me[DSTD_MAX_LAYERS], *re[DSTD_MAX_LAYERS];
   BlockSaved st_in, st_out, enc[DSTD_MAX_LAYERS];
   float* red;
 };
@@ -692,22 +689,32 @@ void carve_model_saved(Carver& cv, ModelSaved& s, int B, int T, int V, int C, in
   const size_t act = (size_t)B * C * T * V;
   s.X0 = cv.take((size_t)B * 6 * T * V);
   carve_block_saved(cv, s.st_in, B, 6, C, T, V);
-  s.y0 = cv.take(act);
-  s.z0 = cv.take(act);
+  s.in.y = cv.take(act);
+  s.in.z = cv.take(act);
   s.hp0 = cv.take(act);
-  s.m0 = cv.take(2 * C * V);  // per BN group (DSTD_TRAIN_PAIRED: 2)
-  s.r0 = cv.take(2 * C * V);
+  s.in.mean = cv.take(2 * C * V);  // per BN group (DSTD_TRAIN_PAIRED: 2)
+  s.in.rstd = cv.take(2 * C * V);
   for (int i = 0; i <= L; ++i) s.h[i] = cv.take(act);
   for (int i = 0; i < L; ++i) {
     carve_block_saved(cv, s.enc[i], B, C, C, T, V);
-    s.yb[i] = cv.take(act);
-    s.ze[i] = cv.take(act);
-    s.me[i] = cv.take(2 * C * V);
-    s.re[i] = cv.take(2 * C * V);
+    s.enc_bn[i].y = cv.take(act);
+    s.enc_bn[i].z = cv.take(act);
+    s.enc_bn[i].mean = cv.take(2 * C * V);
+    s.enc_bn[i].rstd = cv.take(2 * C * V);
   }
   carve_block_saved(cv, s.st_out, B, C, 3, T, V);
   s.o = cv.take((size_t)B * 3 * T * V);
   s.red = cv.take(bn_scratch_floats(B, C, T, V));
+}
+// The model's sites: h[0] = dropout(PReLU(BN(st_in(X0)))) (:306-308) and
+// h[i+1] = PReLU(BN(enc[i](h[i]) + h[i])) (:278-285, Identity residual :247-248).
+BnSite model_in_site(const dstd_model_params* p, const ModelSaved& S, float dropout_p) {
+  float* const out = dropout_p > 0.f ? S.hp0 : S.h[0];
+  return BnSite{&p->bn_in, p->prelu, p->num_feature, S.in.y, nullptr, nullptr, out, S.in.z, S.in.mean, S.in.rstd};
+}
+BnSite model_enc_site(const dstd_model_params* p, const ModelSaved& S, int i) {
+  const SiteSaved& e = S.enc_bn[i];
+  return BnSite{&p->enc_bn[i], p->enc_prelu[i], p->num_feature, e.y, S.h[i], nullptr, S.h[i + 1], e.z, e.mean, e.rstd};
 }
 
 struct ModelWs {
@@ -723,6 +730,64 @@ void carve_model_ws(Carver& cv, ModelWs& w, int B, int T, int V, int C) {
   w.du = cv.take(act);
   w.pp = cv.take(C);
   w.dX0 = cv.take((size_t)B * 6 * T * V);
+}
+
+// ---------------------------------------------------------------------------
+// Refusals.  One function per level, shared by the level's forward and
+// backward entry point; each direction checks its own pointers beside the
+// call.  The first failing check decides the code, and the order is part of
+// the interface (tests/test_train_refusals_host.py holds it): pointers, flags
+// and DSTD_TRAIN_PAIRED parity, then a non-positive shape (DSTD_EINVAL); the
+// envelope (DSTD_ELIMIT); the sizes (DSTD_EWORKSPACE).
+// Kept as they are, for a later change to decide:
+//   - an op with cin = 0 or cout = 0 is DSTD_ELIMIT (ch_ok answers for both
+//     ends of the range), while B = 0 or red = 0 is DSTD_EINVAL;
+//   - a block with cin or cout outside [1, 64] is DSTD_EINVAL here and
+//     DSTD_ELIMIT in the eval forward (block_channels_ok);
+//   - hence a model with num_feature = 65 is DSTD_EINVAL when its blocks have
+//     65 channels too (model_ok's block checks come first) and DSTD_ELIMIT
+//     when they have 64;
+//   - only the model forward compares st_in / st_out's channels with
+//     6 / num_feature / 3, and neither direction looks at enc[i]'s;
+//   - the model backward looks at its gradient pointers after the envelope,
+//     so a NULL gradient with T = 129 is DSTD_ELIMIT;
+//   - both model checks above sit between the envelope and the sizes, which
+//     is why model_call_code stops before the sizes.
+// ---------------------------------------------------------------------------
+int op_call_code(int mode, const float* x, int B, int cin, int cout, int T, int V, int red, const dstd_gc_weights* w,
+                 const float* alpha, const void* saved, size_t saved_bytes) {
+  if (!x || !alpha || !gc_ok(w) || !saved) return DSTD_EINVAL;
+  if (mode != DSTD_MODE_SPATIAL && mode != DSTD_MODE_TEMPORAL) return DSTD_EINVAL;
+  if (B <= 0 || T <= 1 || V <= 0 || red <= 0) return DSTD_EINVAL;
+  if (!shape_ok(B, T, V) || !ch_ok(cin) || !ch_ok(cout) || red > kMaxRed) return DSTD_ELIMIT;
+  if (saved_bytes < dstd_dstdgc_train_saved_bytes_r(mode, B, cin, cout, T, V, red)) return DSTD_EWORKSPACE;
+  return DSTD_OK;
+}
+int block_call_code(const dstd_block_params* p, const float* x, int B, int T, int V, const void* saved,
+                    size_t saved_bytes, unsigned flags) {
+  // pointers, then (training path only) the channel range: block_channels_ok
+  if (!block_ptrs_ok(p) || !block_channels_ok(p)) return DSTD_EINVAL;
+  if (!x || !saved || (flags & ~kTrainFlags)) return DSTD_EINVAL;
+  if ((flags & DSTD_TRAIN_PAIRED) && (B & 1)) return DSTD_EINVAL;
+  if (B <= 0 || T <= 1 || V <= 0) return DSTD_EINVAL;
+  if (!shape_ok(B, T, V)) return DSTD_ELIMIT;
+  if (saved_bytes < dstd_block_train_saved_bytes(B, p->cin, p->cout, T, V)) return DSTD_EWORKSPACE;
+  return DSTD_OK;
+}
+bool sync_ok(const dstd_bn_sync* y, int C, int V) {
+  return !y || (y->fn && y->buf && y->world >= 1 && y->rank >= 0 && y->rank < y->world &&
+                y->buf_floats >= (long long)dstd_bn_sync_buffer_floats(y->world, C, V));
+}
+int model_call_code(const dstd_model_params* p, const float* x, int B, float dropout_p, unsigned long long seed,
+                    const void* saved, unsigned flags, const dstd_bn_sync* sync) {
+  if (!model_ok(p) || !x || !saved || !(dropout_p >= 0.f && dropout_p < 1.f)) return DSTD_EINVAL;
+  if (!sync_ok(sync, p->num_feature, p->V)) return DSTD_EINVAL;
+  if (flags & ~kModelTrainFlags) return DSTD_EINVAL;
+  if ((flags & DSTD_TRAIN_SEED_DEVICE) && dropout_p > 0.f && !seed) return DSTD_EINVAL;
+  if ((flags & DSTD_TRAIN_PAIRED) && (B & 1)) return DSTD_EINVAL;
+  if (B <= 0 || p->T <= 1 || p->V <= 0) return DSTD_EINVAL;
+  if (!shape_ok(B, p->T, p->V) || !ch_ok(p->num_feature)) return DSTD_ELIMIT;
+  return DSTD_OK;
 }
 
 }  // namespace
@@ -747,11 +812,8 @@ int dstd_dstdgc_train_fwd_r(int mode, const float* x, int B, int cin, int cout, 
                             const dstd_gc_weights* w, const float* A, const float* alpha, float* y, void* saved,
                             size_t saved_bytes, void* stream) {
   StreamDeviceGuard dev_guard_(stream, x);
-  if (!x || !y || !A || !alpha || !gc_ok(w) || !saved) return DSTD_EINVAL;
-  if (mode != DSTD_MODE_SPATIAL && mode != DSTD_MODE_TEMPORAL) return DSTD_EINVAL;
-  if (B <= 0 || T <= 1 || V <= 0 || red <= 0) return DSTD_EINVAL;
-  if (!shape_ok(B, T, V) || !ch_ok(cin) || !ch_ok(cout) || red > kMaxRed) return DSTD_ELIMIT;
-  if (saved_bytes < dstd_dstdgc_train_saved_bytes_r(mode, B, cin, cout, T, V, red)) return DSTD_EWORKSPACE;
+  if (!y || !A) return DSTD_EINVAL;
+  if (const int e = op_call_code(mode, x, B, cin, cout, T, V, red, w, alpha, saved, saved_bytes)) return e;
   const OpGeom g(mode, B, cin, cout, T, V, red);
   Carver cv{(char*)saved};
   OpSaved sv;
@@ -768,11 +830,8 @@ int dstd_dstdgc_train_bwd_r(int mode, const float* x, int B, int cin, int cout, 
                             const float* dy, float* dx, const dstd_gc_grads* g, float* dA, float* dalpha,
                             void* workspace, size_t workspace_bytes, void* stream) {
   StreamDeviceGuard dev_guard_(stream, x);
-  if (!x || !dy || !alpha || !gc_ok(w) || !gg_ok(g) || !dA || !dalpha || !saved || !workspace) return DSTD_EINVAL;
-  if (mode != DSTD_MODE_SPATIAL && mode != DSTD_MODE_TEMPORAL) return DSTD_EINVAL;
-  if (B <= 0 || T <= 1 || V <= 0 || red <= 0) return DSTD_EINVAL;
-  if (!shape_ok(B, T, V) || !ch_ok(cin) || !ch_ok(cout) || red > kMaxRed) return DSTD_ELIMIT;
-  if (saved_bytes < dstd_dstdgc_train_saved_bytes_r(mode, B, cin, cout, T, V, red)) return DSTD_EWORKSPACE;
+  if (!dy || !gg_ok(g) || !dA || !dalpha || !workspace) return DSTD_EINVAL;
+  if (const int e = op_call_code(mode, x, B, cin, cout, T, V, red, w, alpha, saved, saved_bytes)) return e;
   if (workspace_bytes < dstd_dstdgc_train_workspace_bytes_r(mode, B, cin, cout, T, V, red))
     return DSTD_EWORKSPACE;
   const OpGeom geo(mode, B, cin, cout, T, V, red);
@@ -782,7 +841,9 @@ int dstd_dstdgc_train_bwd_r(int mode, const float* x, int B, int cin, int cout, 
   Carver cw{(char*)workspace};
   OpWs ws;
   carve_op_ws(cw, ws, {geo});
-  DSTD_TRY(op_bwd(geo, x, w, alpha, sv, dy, dx, g, dA, dalpha, ws, (hipStream_t)stream));
+  Wgrad one((hipStream_t)stream);
+  const TrainCall c{B, T, V, 0.f, 0u, nullptr, (hipStream_t)stream, &one};
+  DSTD_TRY(op_bwd(geo, x, w, alpha, sv, dy, dx, 1.f, g, AdjGrads{dA, dalpha}, ws, c));
   return DSTD_OK;
 }
 
@@ -825,15 +886,14 @@ size_t dstd_block_train_workspace_bytes(int B, int cin, int cout, int T, int V) 
 int dstd_block_train_fwd_ex(const dstd_block_params* p, const float* x, int B, int T, int V, float momentum,
                             float* y, void* saved, size_t saved_bytes, void* stream, unsigned flags) {
   StreamDeviceGuard dev_guard_(stream, x);
-  if (!block_ok(p) || !x || !y || !saved || (flags & ~kTrainFlags)) return DSTD_EINVAL;
-  if ((flags & DSTD_TRAIN_PAIRED) && (B & 1)) return DSTD_EINVAL;
-  if (B <= 0 || T <= 1 || V <= 0) return DSTD_EINVAL;
-  if (!shape_ok(B, T, V)) return DSTD_ELIMIT;
-  if (saved_bytes < dstd_block_train_saved_bytes(B, p->cin, p->cout, T, V)) return DSTD_EWORKSPACE;
+  if (!y) return DSTD_EINVAL;
+  if (const int e = block_call_code(p, x, B, T, V, saved, saved_bytes, flags)) return e;
   Carver cv{(char*)saved};
   BlockSaved S;
   carve_block_saved(cv, S, B, p->cin, p->cout, T, V);
-  DSTD_TRY(block_fwd(p, x, B, T, V, momentum, y, S, (hipStream_t)stream, (int)flags));
+  Wgrad one((hipStream_t)stream);
+  const TrainCall c{B, T, V, momentum, flags, nullptr, (hipStream_t)stream, &one};
+  DSTD_TRY(block_fwd(p, x, y, S, false, c));
   return DSTD_OK;
 }
 
@@ -846,12 +906,8 @@ int dstd_block_train_bwd_ex(const dstd_block_params* p, const float* x, int B, i
                             size_t saved_bytes, const float* dy, float* dx, const dstd_block_grads* g,
                             void* workspace, size_t workspace_bytes, void* stream, unsigned flags) {
   StreamDeviceGuard dev_guard_(stream, x);
-  if (!block_ok(p) || !block_grads_ok(p, g) || !x || !dy || !saved || !workspace) return DSTD_EINVAL;
-  if (flags & ~kTrainFlags) return DSTD_EINVAL;
-  if ((flags & DSTD_TRAIN_PAIRED) && (B & 1)) return DSTD_EINVAL;
-  if (B <= 0 || T <= 1 || V <= 0) return DSTD_EINVAL;
-  if (!shape_ok(B, T, V)) return DSTD_ELIMIT;
-  if (saved_bytes < dstd_block_train_saved_bytes(B, p->cin, p->cout, T, V)) return DSTD_EWORKSPACE;
+  if (!block_grads_ok(p, g) || !dy || !workspace) return DSTD_EINVAL;
+  if (const int e = block_call_code(p, x, B, T, V, saved, saved_bytes, flags)) return e;
   if (workspace_bytes < dstd_block_train_workspace_bytes(B, p->cin, p->cout, T, V)) return DSTD_EWORKSPACE;
   Carver cs{(char*)const_cast<void*>(saved)};
   BlockSaved S;
@@ -859,7 +915,9 @@ int dstd_block_train_bwd_ex(const dstd_block_params* p, const float* x, int B, i
   Carver cw{(char*)workspace};
   BlockWs W;
   carve_block_ws(cw, W, B, T, V, {{p->cin, p->cout}});
-  DSTD_TRY(block_bwd(p, x, B, T, V, S, dy, dx, g, W, (hipStream_t)stream, (int)flags));
+  Wgrad one((hipStream_t)stream);
+  const TrainCall c{B, T, V, 0.f, flags, nullptr, (hipStream_t)stream, &one};
+  DSTD_TRY(block_bwd(p, x, S, dy, dx, false, nullptr, g, W, c));
   return DSTD_OK;
 }
 
@@ -892,11 +950,6 @@ size_t dstd_bn_sync_buffer_floats(int world, int num_feature, int V) {
   return std::max((size_t)std::max(world, 1) * 2 * cv * 3, 2 * cv * 2 + 2);
 }
 
-static bool sync_ok(const dstd_bn_sync* y, int C, int V) {
-  return !y || (y->fn && y->buf && y->world >= 1 && y->rank >= 0 && y->rank < y->world &&
-                y->buf_floats >= (long long)dstd_bn_sync_buffer_floats(y->world, C, V));
-}
-
 int dstd_model_train_fwd_ex(const dstd_model_params* p, const float* x, int B, float momentum, float dropout_p,
                             unsigned long long seed, float* y, void* saved, size_t saved_bytes, void* stream,
                             unsigned flags) {
@@ -907,15 +960,10 @@ int dstd_model_train_fwd_sync(const dstd_model_params* p, const float* x, int B,
                               unsigned long long seed, float* y, void* saved, size_t saved_bytes, void* stream,
                               unsigned flags, const dstd_bn_sync* sync) {
   StreamDeviceGuard dev_guard_(stream, x);
-  if (!model_ok(p) || !x || !y || !saved || !(dropout_p >= 0.f && dropout_p < 1.f)) return DSTD_EINVAL;
-  if (!sync_ok(sync, p->num_feature, p->V)) return DSTD_EINVAL;
-  if (flags & ~kModelTrainFlags) return DSTD_EINVAL;
-  if ((flags & DSTD_TRAIN_SEED_DEVICE) && dropout_p > 0.f && !seed) return DSTD_EINVAL;
-  if ((flags & DSTD_TRAIN_PAIRED) && (B & 1)) return DSTD_EINVAL;
-  const int run = (int)flags;
+  if (!y) return DSTD_EINVAL;
+  if (const int e = model_call_code(p, x, B, dropout_p, seed, saved, flags, sync)) return e;
   const int T = p->T, V = p->V, C = p->num_feature, L = p->num_layers;
-  if (B <= 0 || T <= 1 || V <= 0) return DSTD_EINVAL;
-  if (!shape_ok(B, T, V) || !ch_ok(C)) return DSTD_ELIMIT;
+  // (the forward only: model_call_code's list)
   if (p->st_in.cin != 6 || p->st_in.cout != C || p->st_out.cin != C || p->st_out.cout != 3) return DSTD_EINVAL;
   if (saved_bytes < dstd_model_train_saved_bytes(B, T, V, C, L)) return DSTD_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
@@ -925,8 +973,8 @@ int dstd_model_train_fwd_sync(const dstd_model_params* p, const float* x, int B,
   const size_t act = (size_t)B * C * T * V;
   // the blocks' second spatial ops build their adjacency on a second stream
   // (block_fwd); joined at each block and by the destructor on any return
-  Wgrad side((flags & DSTD_TRAIN_ONE_STREAM) ? nullptr : wgrad_acquire());
-  side.main = s;
+  Wgrad side(s, (flags & DSTD_TRAIN_ONE_STREAM) ? nullptr : wgrad_acquire());
+  const TrainCall c{B, T, V, momentum, flags, sync, s, &side};
   DSTD_TRY(prep_nctv(x, B, T, V, 3, S.X0, s));                                   // :298-303
   {  // every block's packed conv weights, kMaxCopyJobs per launch
     CopyJobs js;
@@ -943,47 +991,15 @@ int dstd_model_train_fwd_sync(const dstd_model_params* p, const float* x, int B,
     DSTD_TRY(add(&p->st_out, S.st_out));
     DSTD_TRY(copy_jobs(js, s));
   }
-  DSTD_TRY(block_fwd(&p->st_in, S.X0, B, T, V, momentum, S.y0, S.st_in, s, run, sync, true, &side));  // :305
-  BnFwd b0;                                                                      // :306-308
-  b0.x = S.y0;
-  b0.gamma = p->bn_in.weight;
-  b0.beta = p->bn_in.bias;
-  b0.running_mean = const_cast<float*>(p->bn_in.running_mean);
-  b0.running_var = const_cast<float*>(p->bn_in.running_var);
-  b0.momentum = momentum;
-  b0.eps = p->bn_in.eps;
-  b0.prelu = p->prelu;
-  b0.out = dropout_p > 0.f ? S.hp0 : S.h[0];
-  b0.zsave = S.z0;
-  b0.mean = S.m0;
-  b0.rstd = S.r0;
-  b0.use_running = (run & DSTD_TRAIN_RUNNING_STATS) != 0;
-  b0.groups = (run & DSTD_TRAIN_PAIRED) ? 2 : 1;
-  b0.sync = sync;
-  DSTD_TRY(bn_train_fwd(b0, B, C, T, V, S.red, s));
-  if (dropout_p > 0.f) DSTD_TRY(dropout(S.hp0, S.h[0], act, dropout_p, seed, s, (flags & DSTD_TRAIN_SEED_DEVICE) != 0));  // do_in
-  for (int i = 0; i < L; ++i) {                                                  // :310-311
-    DSTD_TRY(block_fwd(&p->enc[i], S.h[i], B, T, V, momentum, S.yb[i], S.enc[i], s, run, sync, true, &side));
-    BnFwd be;  // BN(block(h) + h) -> PReLU  (:278-285, Identity residual :247-248)
-    be.x = S.yb[i];
-    be.x2 = S.h[i];
-    be.gamma = p->enc_bn[i].weight;
-    be.beta = p->enc_bn[i].bias;
-    be.running_mean = const_cast<float*>(p->enc_bn[i].running_mean);
-    be.running_var = const_cast<float*>(p->enc_bn[i].running_var);
-    be.momentum = momentum;
-    be.eps = p->enc_bn[i].eps;
-    be.prelu = p->enc_prelu[i];
-    be.out = S.h[i + 1];
-    be.zsave = S.ze[i];
-    be.mean = S.me[i];
-    be.rstd = S.re[i];
-    be.use_running = (run & DSTD_TRAIN_RUNNING_STATS) != 0;
-    be.groups = (run & DSTD_TRAIN_PAIRED) ? 2 : 1;
-    be.sync = sync;
-    DSTD_TRY(bn_train_fwd(be, B, C, T, V, S.red, s));
+  DSTD_TRY(block_fwd(&p->st_in, S.X0, S.in.y, S.st_in, true, c));  // :305
+  DSTD_TRY(site_fwd(model_in_site(p, S, dropout_p), c, S.red));    // :306-308
+  if (dropout_p > 0.f)                                             // do_in
+    DSTD_TRY(dropout(S.hp0, S.h[0], act, dropout_p, seed, s, (flags & DSTD_TRAIN_SEED_DEVICE) != 0));
+  for (int i = 0; i < L; ++i) {  // :310-311
+    DSTD_TRY(block_fwd(&p->enc[i], S.h[i], S.enc_bn[i].y, S.enc[i], true, c));
+    DSTD_TRY(site_fwd(model_enc_site(p, S, i), c, S.red));
   }
-  DSTD_TRY(block_fwd(&p->st_out, S.h[L], B, T, V, momentum, S.o, S.st_out, s, run, sync, true, &side));  // :313
+  DSTD_TRY(block_fwd(&p->st_out, S.h[L], S.o, S.st_out, true, c));  // :313
   DSTD_TRY(out_ntvc(S.o, x, B, T, V, 3, y, s));                                       // :314-315
   return DSTD_OK;
 }
@@ -1006,16 +1022,10 @@ int dstd_model_train_bwd_sync(const dstd_model_params* p, const float* x, int B,
                               const dstd_model_grads* g, float* dx, void* workspace, size_t workspace_bytes,
                               void* stream, unsigned flags, const dstd_bn_sync* sync) {
   StreamDeviceGuard dev_guard_(stream, x);
-  if (!model_ok(p) || !g || !x || !dy || !saved || !workspace || !(dropout_p >= 0.f && dropout_p < 1.f))
-    return DSTD_EINVAL;
-  if (!sync_ok(sync, p->num_feature, p->V)) return DSTD_EINVAL;
-  if (flags & ~kModelTrainFlags) return DSTD_EINVAL;
-  if ((flags & DSTD_TRAIN_SEED_DEVICE) && dropout_p > 0.f && !seed) return DSTD_EINVAL;
-  if ((flags & DSTD_TRAIN_PAIRED) && (B & 1)) return DSTD_EINVAL;
-  const int run = (int)flags;
+  if (!g || !dy || !workspace) return DSTD_EINVAL;
+  if (const int e = model_call_code(p, x, B, dropout_p, seed, saved, flags, sync)) return e;
   const int T = p->T, V = p->V, C = p->num_feature, L = p->num_layers;
-  if (B <= 0 || T <= 1 || V <= 0) return DSTD_EINVAL;
-  if (!shape_ok(B, T, V) || !ch_ok(C)) return DSTD_ELIMIT;
+  // (after the envelope: model_call_code's list)
   if (!block_grads_ok(&p->st_in, &g->st_in) || !block_grads_ok(&p->st_out, &g->st_out) || !bng_ok(g->bn_in) ||
       !g->prelu)
     return DSTD_EINVAL;
@@ -1031,53 +1041,22 @@ int dstd_model_train_bwd_sync(const dstd_model_params* p, const float* x, int B,
   ModelWs W;
   carve_model_ws(cw, W, B, T, V, C);
   const size_t act = (size_t)B * C * T * V;
-  Wgrad wg((flags & DSTD_TRAIN_ONE_STREAM) ? nullptr : wgrad_acquire());
-  wg.main = s;
+  Wgrad wg(s, (flags & DSTD_TRAIN_ONE_STREAM) ? nullptr : wgrad_acquire());
+  const TrainCall c{B, T, V, 0.f, flags, sync, s, &wg};
   DSTD_TRY(out_ntvc_bwd(dy, B, T, V, 3, W.dO, s));
   float* dha = W.dha;
   float* dhb = W.dhb;
-  DSTD_TRY(block_bwd(&p->st_out, S.h[L], B, T, V, S.st_out, W.dO, dha, &g->st_out, W.blk, s, run, true, nullptr,
-                     sync, &wg));
+  float* const red = W.blk.op.red;
+  DSTD_TRY(block_bwd(&p->st_out, S.h[L], S.st_out, W.dO, dha, true, nullptr, &g->st_out, W.blk, c));
   for (int i = L - 1; i >= 0; --i) {
-    BnBwd be;
-    be.x = S.yb[i];
-    be.x2 = S.h[i];
-    be.zsave = S.ze[i];
-    be.prelu = p->enc_prelu[i];
-    be.dout = dha;
-    be.mean = S.me[i];
-    be.rstd = S.re[i];
-    be.gamma = p->enc_bn[i].weight;
-    be.du = W.du;
-    be.dgamma = g->enc_bn[i].weight;
-    be.dbeta = g->enc_bn[i].bias;
-    be.use_running = (run & DSTD_TRAIN_RUNNING_STATS) != 0;
-    be.groups = (run & DSTD_TRAIN_PAIRED) ? 2 : 1;
-    be.sync = sync;
-    DSTD_TRY(bn_train_bwd(be, B, C, T, V, W.blk.op.red, g->enc_prelu[i], s));
+    DSTD_TRY(site_bwd(model_enc_site(p, S, i), c, dha, BnSiteGrads{W.du, &g->enc_bn[i], g->enc_prelu[i]}, red));
     // u = block(h) + h: dh = du (identity path) + block backward
-    DSTD_TRY(block_bwd(&p->enc[i], S.h[i], B, T, V, S.enc[i], W.du, dhb, &g->enc[i], W.blk, s, run, true, W.du,
-                       sync, &wg));
+    DSTD_TRY(block_bwd(&p->enc[i], S.h[i], S.enc[i], W.du, dhb, true, W.du, &g->enc[i], W.blk, c));
     std::swap(dha, dhb);
   }
   if (dropout_p > 0.f) DSTD_TRY(dropout(dha, dha, act, dropout_p, seed, s, (flags & DSTD_TRAIN_SEED_DEVICE) != 0));
-  BnBwd b0;
-  b0.x = S.y0;
-  b0.zsave = S.z0;
-  b0.prelu = p->prelu;
-  b0.dout = dha;
-  b0.mean = S.m0;
-  b0.rstd = S.r0;
-  b0.gamma = p->bn_in.weight;
-  b0.du = W.du;
-  b0.dgamma = g->bn_in.weight;
-  b0.dbeta = g->bn_in.bias;
-  b0.use_running = (run & DSTD_TRAIN_RUNNING_STATS) != 0;
-  b0.groups = (run & DSTD_TRAIN_PAIRED) ? 2 : 1;
-  b0.sync = sync;
-  DSTD_TRY(bn_train_bwd(b0, B, C, T, V, W.blk.op.red, g->prelu, s));
-  DSTD_TRY(block_bwd(&p->st_in, S.X0, B, T, V, S.st_in, W.du, dx ? W.dX0 : nullptr, &g->st_in, W.blk, s, run, true,
-                     nullptr, sync, &wg));
+  DSTD_TRY(site_bwd(model_in_site(p, S, dropout_p), c, dha, BnSiteGrads{W.du, &g->bn_in, g->prelu}, red));
+  DSTD_TRY(block_bwd(&p->st_in, S.X0, S.st_in, W.du, dx ? W.dX0 : nullptr, true, nullptr, &g->st_in, W.blk, c));
   if (dx) DSTD_TRY(prep_nctv_bwd(W.dX0, dy, B, T, V, 3, dx, s));  // :298-303, 315
   DSTD_TRY(wg.join());
   return DSTD_OK;
