@@ -313,6 +313,13 @@ def lib():
         if hasattr(L, "dstd_batch_gather"):
             L.dstd_batch_gather.restype = ci
             L.dstd_batch_gather.argtypes = [ctypes.POINTER(SeqStore), vp, ci, vp, vp, vp, vp, vp]
+        # rollout of the eval forward (include/dstd_gcn_predict.h; absent from
+        # an earlier revision's library loaded for an A/B)
+        if hasattr(L, "dstd_model_predict"):
+            L.dstd_model_predict_workspace_bytes.restype = sz
+            L.dstd_model_predict_workspace_bytes.argtypes = [ci] * 5
+            L.dstd_model_predict.restype = ci
+            L.dstd_model_predict.argtypes = [ctypes.POINTER(ModelParams), vp, ci, ci, ci, vp, vp, sz, vp, uf]
         _lib = L
     return _lib
 
@@ -337,6 +344,8 @@ LOSS_EXPORTS = ("dstd_losses_workspace_bytes", "dstd_losses_fwd", "dstd_losses_b
 TAPS_EXPORTS = ("dstd_block_taps_workspace_bytes", "dstd_model_taps_workspace_bytes", "dstd_block_fwd_taps",
                 "dstd_model_fwd_taps")
 DATA_EXPORTS = ("dstd_batch_gather",)
+PREDICT_EXPORTS = ("dstd_model_predict_workspace_bytes", "dstd_model_predict")
+PREDICT_MAX_WINDOWS = 64  # include/dstd_gcn_predict.h DSTD_PREDICT_MAX_WINDOWS
 
 
 ARITHMETICS = ("split", "fp32")

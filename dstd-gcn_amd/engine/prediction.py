@@ -336,8 +336,17 @@ class PredictionEngine:
 
     # ------------------------------------------------------------------
     def test(self, test_loader, input_n=10, eval_frame=None, dim_used=None, joint_to_ignore=None, joint_equal=None,
-             time_tsfm=None, scale_tsfm=None, action=None, save_path=None):
+             time_tsfm=None, scale_tsfm=None, action=None, save_path=None, horizon=None):
+        """``horizon`` (None: the reference's path, one forward of the padded
+        window): evaluate a rollout instead -- the first ``input_n`` frames of
+        ``inputs`` are the observations, ``model.predict`` returns the
+        ``horizon`` frames after them in one native call, and ``all_seqs`` must
+        hold ``input_n + horizon`` frames; ``eval_frame`` may reach
+        ``horizon - 1``."""
         assert eval_frame is not None
+        if horizon is not None and time_tsfm is not None:
+            raise ValueError("test: a time transform of a window does not chain over windows; "
+                             "horizon needs time_tsfm=None")
         dev = self.device
         sums = torch.zeros(len(eval_frame), dtype=torch.float32, device=dev)
         N = 0
@@ -361,7 +370,10 @@ class PredictionEngine:
                     continue  # round-robin batch sharding over the ranks
                 inputs = _to_dev(inputs, dev)
                 all_seqs = all_seqs.float().to(dev, non_blocking=True).contiguous()
-                outputs = self.inverse(self.model(self.transform(inputs), False))
+                if horizon is not None:
+                    outputs = self._rollout(inputs, all_seqs, input_n, horizon)
+                else:
+                    outputs = self.inverse(self.model(self.transform(inputs), False))
                 if isinstance(outputs, list):
                     outputs = outputs[0]
                     n, t = outputs.shape[:2]
@@ -403,6 +415,17 @@ class PredictionEngine:
                 self._save_results(save_path, save_results, rank, world)
         # t_l.avg of the reference = sum over (batch, frame) of metric_k / (N * frames)
         return float(t_metric.mean()), t_metric
+
+    def _rollout(self, inputs, all_seqs, input_n, horizon):
+        """test(horizon=...): the model's ``predict`` on the observed frames of
+        one batch, in the engine's [n, horizon, dims] form."""
+        if isinstance(inputs, list):
+            raise ValueError("test: horizon takes one input tensor per batch, not a list")
+        if all_seqs.shape[1] != input_n + horizon:
+            raise ValueError(f"test: horizon {horizon} after {input_n} observed frames needs all_seqs of "
+                             f"{input_n + horizon} frames, got {all_seqs.shape[1]}")
+        observed = self.transform(inputs)[:, :input_n].contiguous()
+        return self.inverse(self.model.model.predict(observed, horizon))
 
     @staticmethod
     def _presharded_real(sampler):

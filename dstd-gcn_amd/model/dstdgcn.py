@@ -1111,6 +1111,61 @@ class DSTDGCN(_NativeModule):
         native.check(code, "dstd_model_fwd_taps")
         return y, out
 
+    def predict(self, observed, horizon=None):
+        """The ``horizon`` frames (default ``output_time_frame``) that follow
+        ``observed`` [N, input_time_frame, V, 3], as [N, horizon, V, 3]: one
+        native call (include/dstd_gcn_predict.h) that pads the observed frames
+        into a window with copies of the last one, as the reference's datasets
+        do, runs the eval forward, and for a horizon beyond
+        ``output_time_frame`` feeds the last ``input_time_frame`` frames of
+        what is known so far -- observations as given, predictions appended --
+        into the next window, without leaving the device.  What a loop of
+        ``self(x)`` over windows built with torch indexing returns, bit for
+        bit.  Eval mode only, detached, no autograd; honours ``gc_arithmetic``.
+        The folded constants are shared with ``self(x)`` of the same batch
+        size (``_forward_native``)."""
+        if self.training:
+            raise RuntimeError("DSTDGCN.predict rolls the eval forward out: call .eval() first")
+        n, tin, v, c = observed.shape
+        assert tin == self.input_time_frame
+        if c != self.input_channels // 2 or v != self.joints_to_consider:
+            raise ValueError(f"DSTDGCN: expected [N, {tin}, {self.joints_to_consider}, {self.input_channels // 2}], "
+                             f"got {list(observed.shape)}")
+        horizon = self.output_time_frame if horizon is None else int(horizon)
+        if horizon < 1:
+            raise ValueError(f"DSTDGCN.predict: horizon {horizon} < 1")
+        if -(-horizon // self.output_time_frame) > native.PREDICT_MAX_WINDOWS:
+            raise ValueError(f"DSTDGCN.predict: horizon {horizon} needs more than {native.PREDICT_MAX_WINDOWS} "
+                             f"windows of {self.output_time_frame} frames")
+        native.lib()
+        observed = observed.detach().contiguous()
+        native.require_device(observed, "observed")
+        flags = native.arith_flags(self.gc_arithmetic)
+        if type(observed) is not torch.Tensor or torch.compiler.is_compiling():
+            # tracing: the custom op, whose inputs name every tensor the call reads
+            params, buffers = self._tree.get(self)
+            return torch.ops.dstd.dstdgcn_predict(observed, params + buffers, self._dstd_uid, horizon, flags)
+        with torch.no_grad():
+            out = observed.new_empty(n, horizon, v, c)
+            if n:
+                self._predict_native(observed, out, arith=flags)
+        return out
+
+    def _predict_native(self, obs, out, arith=None):
+        """One rollout through dstd_model_predict, on the forward's workspace
+        and constants (``_claim_workspace``)."""
+        L = native.lib()
+        n, tin, v, _ = obs.shape
+        dev = obs.device
+        t = tin + self.output_time_frame
+        p = self._native_params()
+        flags = (native.arith_flags(self.gc_arithmetic) if arith is None else arith) | self._dstd_fwd_flags
+        nbytes = L.dstd_model_predict_workspace_bytes(n, t, v, self.num_feature, self.num_layers)
+        ws, flags = self._claim_workspace(dev, nbytes, n, flags)
+        code = L.dstd_model_predict(p, native.ptr(obs, "observed"), n, tin, out.shape[1], native.ptr(out, "out"),
+                                    ws.data_ptr(), ws.numel(), native.stream_handle(dev), flags)
+        native.check(code, "dstd_model_predict")
+
     def forward_pair(self, x1, x2):
         """``(self(x1), self(x2))`` -- PredictionEngine.train's forward of a
         batch and of its time reversal (engine/prediction.py:231-287) -- as
@@ -1192,6 +1247,20 @@ class DSTDGCN(_NativeModule):
         run.refresh = refresh
         return run
 
+    def _claim_workspace(self, dev, nbytes, n, flags):
+        """(workspace, flags) of an eval call at batch size ``n``, after
+        ``_native_params``: the flags carry DSTD_FWD_REUSE_CONSTANTS when the
+        buffer still holds this model's constants (``_forward_native``).  The
+        forward and ``predict`` lay the constants out alike at the start of the
+        buffer and claim it under one tag, so either reuses the other's."""
+        try:
+            versions = tuple(map(_VERSION, self._native_tensors))
+            tag = (self._dstd_uid, self._dstd_gen, self._native[0], n, flags, versions)
+        except RuntimeError:  # "Inference tensors do not track version counter"
+            tag = None
+        ws, reuse = native.workspace_claim(dev, nbytes, tag)
+        return ws, (flags | native.FWD_REUSE_CONSTANTS) if reuse else flags
+
     def _forward_native(self, x, y, prof=None, arith=None):
         """One eval forward through dstd_model_fwd_ex.  The folded constants
         and split-f16 weight images a forward leaves in the workspace are
@@ -1207,15 +1276,8 @@ class DSTDGCN(_NativeModule):
             prof = getattr(self, "_dstd_profile", None)
         p = self._native_params()
         flags = (native.arith_flags(self.gc_arithmetic) if arith is None else arith) | self._dstd_fwd_flags
-        try:
-            versions = tuple(map(_VERSION, self._native_tensors))
-            tag = (self._dstd_uid, self._dstd_gen, self._native[0], n, flags, versions)
-        except RuntimeError:  # "Inference tensors do not track version counter"
-            tag = None
         nbytes = L.dstd_model_workspace_bytes(n, t, v, self.num_feature, self.num_layers)
-        ws, reuse = native.workspace_claim(dev, nbytes, tag)
-        if reuse:
-            flags |= native.FWD_REUSE_CONSTANTS
+        ws, flags = self._claim_workspace(dev, nbytes, n, flags)
         code = L.dstd_model_fwd_ex(p, native.ptr(x, "x"), n, native.ptr(y, "y"), ws.data_ptr(), ws.numel(),
                                    native.stream_handle(dev), flags, prof)
         native.check(code, "dstd_model_fwd_ex")
@@ -1272,6 +1334,24 @@ def _op_dstdgcn_forward(x: torch.Tensor, tensors: List[torch.Tensor], uid: int, 
 @_op_dstdgcn_forward.register_fake
 def _(x, tensors, uid, flags):
     return torch.empty_like(x)
+
+
+@torch.library.custom_op("dstd::dstdgcn_predict", mutates_args=())
+def _op_dstdgcn_predict(observed: torch.Tensor, tensors: List[torch.Tensor], uid: int, horizon: int,
+                        flags: int) -> torch.Tensor:
+    """DSTDGCN.predict -> dstd_model_predict (no counterpart in the reference:
+    its callers loop over windows in Python)."""
+    n, _, v, c = observed.shape
+    out = observed.new_empty(n, horizon, v, c)
+    if n:
+        _instance(uid)._predict_native(observed.contiguous(), out, arith=flags)
+    return out
+
+
+@_op_dstdgcn_predict.register_fake
+def _(observed, tensors, uid, horizon, flags):
+    n, _, v, c = observed.shape
+    return observed.new_empty(n, horizon, v, c)
 
 
 # Training directions (SURVEY §8(b), §8(f) row 1): forward ops return the

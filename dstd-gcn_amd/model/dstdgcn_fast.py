@@ -447,6 +447,17 @@ class DSTDGCN(_Shadowed):
         self._sync(sh)
         return sh(x)
 
+    def predict(self, observed, horizon=None):
+        """``dstdgcn.DSTDGCN.predict`` through the shadow model: the ``horizon``
+        frames after ``observed`` [N, input_time_frame, V, 3] in one native
+        call.  Eval mode only, detached."""
+        if self.training:
+            raise RuntimeError("DSTDGCN.predict rolls the eval forward out: call .eval() first")
+        native.require_device(observed, "observed")
+        sh = self._shadow_for(observed.device)
+        self._sync(sh)
+        return sh.predict(observed, horizon)
+
     def forward_pair(self, x1, x2):
         """``(self(x1), self(x2))`` as one paired native train step
         (dstdgcn.DSTDGCN.forward_pair: per-half BatchNorm statistics, running
