@@ -710,6 +710,38 @@ void carve_model(Carver& cv, ModelLayout& L, int B, int T, int V, int C, int lay
   carve_scratch(cv, L.sc, B, T, V);
 }
 
+// The forward's blocks run[0 .. num_layers + 2): conv_st_in -> bn_in -> prelu
+// (dropout is identity in eval); encoders x = prelu_e(bn_e(DSTDGCB(x) + x));
+// conv_st_out + output residual written straight into y [B][T][V][3].
+// Buffers rotate over act[0..2].
+void model_block_runs(BlockRun* run, const dstd_model_params* p, const ModelLayout& L, const float* x, float* y,
+                      bool one_launch) {
+  const int L_ = p->num_layers, NB = L_ + 2;
+  float *cur = L.act[0], *h = L.act[1], *out = L.act[2];
+  run[0] = BlockRun{&p->st_in, &L.f_in, cur, h, out, BlockTail{TEPI_IN, nullptr, L.bnin_s, L.bnin_h, p->prelu, nullptr}};
+  for (int i = 0; i < L_; ++i) {
+    float* t = cur;  // x: the previous block's y, h: its x, y: its h
+    cur = out;
+    out = h;
+    h = t;
+    run[1 + i] = BlockRun{&p->enc[i], &L.f_enc[i], cur, h, out,
+                          BlockTail{TEPI_ENC, cur, L.ebn_s[i], L.ebn_h[i], p->enc_prelu[i], nullptr}};
+  }
+  // conv_st_out's h is [B][T][V][3]: in an act buffer, sample n's rows lie
+  // inside the 64-channel slice of sample 3n / 64, which that sample's
+  // workgroup may still be reading or writing as an encoder block's
+  // activation -- between launches every encoder block was over before
+  // conv_st_out began.  In the one-launch schedule it goes to the temporal
+  // adjacency scratch, which no launch of that schedule touches (every
+  // temporal adjacency is built in LDS) and which holds B V T T floats or more.
+  run[NB - 1] = BlockRun{&p->st_out, &L.f_out, out, one_launch ? L.sc.adj_t : h, y,
+                         BlockTail{TEPI_OUT, x, nullptr, nullptr, nullptr, nullptr}};
+  for (int b = 0; b + 1 < NB; ++b) {
+    run[b].tail.next = run[b + 1].p;
+    run[b].tail.next_f = run[b + 1].f;
+  }
+}
+
 hipError_t to_layout(const float* src, float* dst, int B, int C, int TV, int to_ntvc, hipStream_t s) {
   TransposeArgs t{src, dst, B, C, TV, to_ntvc};
   return launch_transpose(t, s);
@@ -979,33 +1011,9 @@ int model_fwd(const dstd_model_params* p, const float* x, int B, float* y, void*
   const dstd_launch* first = pl.launch + (pl.prep ? 1 : 0);  // (PREP: step 4)
   const bool one_launch = first->kind == DSTD_LAUNCH_MODEL;
 
-  // conv_st_in -> bn_in -> prelu (dropout is identity in eval); encoders
-  // x = prelu_e(bn_e(DSTDGCB(x) + x)); conv_st_out + output residual written
-  // straight into y [B][T][V][3].  Buffers rotate over act[0..2].
   BlockRun run[kPlanMaxBlocks];
-  float *cur = L.act[0], *h = L.act[1], *out = L.act[2];
-  run[0] = BlockRun{&p->st_in, &L.f_in, cur, h, out, BlockTail{TEPI_IN, nullptr, L.bnin_s, L.bnin_h, p->prelu, nullptr}};
-  for (int i = 0; i < L_; ++i) {
-    float* t = cur;  // x: the previous block's y, h: its x, y: its h
-    cur = out;
-    out = h;
-    h = t;
-    run[1 + i] = BlockRun{&p->enc[i], &L.f_enc[i], cur, h, out,
-                          BlockTail{TEPI_ENC, cur, L.ebn_s[i], L.ebn_h[i], p->enc_prelu[i], nullptr}};
-  }
-  // conv_st_out's h is [B][T][V][3]: in an act buffer, sample n's rows lie
-  // inside the 64-channel slice of sample 3n / 64, which that sample's
-  // workgroup may still be reading or writing as an encoder block's
-  // activation -- between launches every encoder block was over before
-  // conv_st_out began.  In the one-launch schedule it goes to the temporal
-  // adjacency scratch, which no launch of that schedule touches (every
-  // temporal adjacency is built in LDS) and which holds B V T T floats or more.
-  run[NB - 1] = BlockRun{&p->st_out, &L.f_out, out, one_launch ? L.sc.adj_t : h, y,
-                         BlockTail{TEPI_OUT, x, nullptr, nullptr, nullptr, nullptr}};
-  for (int b = 0; b + 1 < NB; ++b) {
-    run[b].tail.next = run[b + 1].p;
-    run[b].tail.next_f = run[b + 1].f;
-  }
+  model_block_runs(run, p, L, x, y, one_launch);
+
 
   // (4) constants (DSTD_FWD_REUSE_CONSTANTS: still in the workspace) and PREP
   Prof pf;
@@ -1046,7 +1054,7 @@ int model_fwd(const dstd_model_params* p, const float* x, int B, float* y, void*
     if (taps && l->num_blocks != 1) return hipErrorInvalidValue;
     switch (l->kind) {
       case DSTD_LAUNCH_MODEL: {
-        ModelChainArgs c{};  // the encoder blocks set the shared geometry: they go first
+        ModelChain c{};  // the encoder blocks set the shared geometry: they go first
         for (int i = 0; i < NB; ++i) {
           const int b = i < L_ ? 1 + i : i == L_ ? 0 : NB - 1;
           DSTD_TRY(fused_args(A[b], pl.blk[b], &ba));
@@ -1101,3 +1109,97 @@ int dstd_event_elapsed_ms(void* start, void* stop, float* ms) {
 }
 
 }  // extern "C"
+
+// ---- host-side probe of the chain appends (tests/test_chain_host.py) -------
+// Not part of the C ABI.  Builds the blocks of a num_feature = 64 model forward
+// at B = 256 as model_fwd does (carve_model, plan_model on 256 compute units,
+// model_block_runs, build_block_args, fused_args) over made-up addresses that
+// nothing dereferences, XORs xor_word into the 32-bit word at byte_offset of
+// block's BlockFusedArgs (block 0 conv_st_in, 1.. the encoders, layers + 1
+// conv_st_out) and runs the appends of the plan's whole-forward launch
+// (whole_model) or of its run of encoder blocks, launching nothing.  Returns
+// 0: every block accepted and the launch's arguments rebuild (*_chain_block) to
+// exactly the blocks appended; 1: an append refused; 2: accepted, but a rebuild
+// differs; DSTD_EINVAL: no such chain, block or word.
+namespace {
+
+struct FakeAddresses {
+  uintptr_t next;
+  const float* operator()() { return reinterpret_cast<const float*>(next += 4096); }
+};
+void fake_block_params(dstd_block_params& p, int cin, int cout, FakeAddresses& fake) {
+  p.cin = cin;
+  p.cout = cout;
+  for (const float** q : {&p.A_s, &p.W_s, &p.R_s, &p.A_t, &p.R_t, &p.alpha_sm, &p.alpha_tm, &p.prelu, &p.res_w, &p.res_b})
+    *q = fake();
+  for (dstd_gc_weights* w : {&p.conv_s[0], &p.conv_s[1], &p.conv_t})
+    for (const float** q : {&w->wf, &w->bf, &w->wm1, &w->bm1, &w->wm2, &w->bm2, &w->wrm, &w->brm}) *q = fake();
+}
+
+}  // namespace
+
+extern "C" int dstd_debug_chain_probe(int T, int V, int layers, int whole_model, int block, int byte_offset,
+                                      unsigned xor_word) {
+  constexpr int B = 256, C = 64, cus = 256;
+  const int NB = layers + 2;
+  if (layers < 1 || model_shape_code(B, T, V, C, layers) != DSTD_OK || block < 0 || block >= NB || byte_offset < 0 ||
+      byte_offset % 4 || byte_offset + 4 > (int)sizeof(BlockFusedArgs))
+    return DSTD_EINVAL;
+  FakeAddresses fake{uintptr_t(1) << 32};
+  dstd_model_params p{};
+  p.T = T;
+  p.V = V;
+  p.in_channels = 6;
+  p.num_feature = C;
+  p.num_layers = layers;
+  fake_block_params(p.st_in, 6, C, fake);
+  fake_block_params(p.st_out, C, 3, fake);
+  p.prelu = fake();
+  for (int i = 0; i < layers; ++i) {
+    fake_block_params(p.enc[i], C, C, fake);
+    p.enc_prelu[i] = fake();
+  }
+  const float* x = fake();
+  float* y = const_cast<float*>(fake());
+  Carver cv{reinterpret_cast<char*>(uintptr_t(1) << 40)};
+  ModelLayout L;
+  carve_model(cv, L, B, T, V, C, layers, 6, 3);
+  Plan pl;
+  plan_model(pl, B, T, V, C, layers, cus, whole_model ? 0u : DSTD_FWD_SEPARATE_ENDS, false, 0);
+  const dstd_launch* l = pl.launch;
+  const int kind = whole_model ? DSTD_LAUNCH_MODEL : DSTD_LAUNCH_ENC_RUN;
+  while (l < pl.launch + pl.n && l->kind != kind) ++l;
+  if (l == pl.launch + pl.n || block < l->first_block || block >= l->first_block + l->num_blocks) return DSTD_EINVAL;
+  BlockRun run[kPlanMaxBlocks];
+  model_block_runs(run, &p, L, x, y, whole_model != 0);
+  BlockFusedArgs ba[kPlanMaxBlocks];
+  for (int b = l->first_block; b < l->first_block + l->num_blocks; ++b) {
+    BlockArgs A;
+    build_block_args(A, run[b], L.sc, B, T, V, pl.blk[b], b == 0 ? x : nullptr);
+    if (fused_args(A, pl.blk[b], &ba[b]) != hipSuccess) return DSTD_EINVAL;
+  }
+  unsigned word;
+  memcpy(&word, (const char*)&ba[block] + byte_offset, 4);
+  word ^= xor_word;
+  memcpy((char*)&ba[block] + byte_offset, &word, 4);
+  bool same = true;
+  if (whole_model) {
+    ModelChain c{};
+    for (int i = 0; i < NB; ++i)  // as model_fwd: the encoder blocks first
+      if (model_chain_append(&c, ba[i < layers ? 1 + i : i == layers ? 0 : NB - 1]) != hipSuccess) return 1;
+    if (!model_chain_complete(c)) return 1;
+    for (int b = 0; b < NB; ++b) {
+      const BlockFusedArgs r = model_chain_block(c.a, b == 0 ? CHAIN_IN : b == NB - 1 ? CHAIN_OUT : CHAIN_ENC, b - 1);
+      same = same && !memcmp(&r, &ba[b], sizeof(r));
+    }
+  } else {
+    EncChainArgs c{};
+    for (int b = l->first_block; b < l->first_block + l->num_blocks; ++b)
+      if (enc_chain_append(&c, ba[b]) != hipSuccess) return 1;
+    for (int i = 0; i < c.nblk; ++i) {
+      const BlockFusedArgs r = enc_chain_block(c, i);
+      same = same && !memcmp(&r, &ba[l->first_block + i], sizeof(r));
+    }
+  }
+  return same ? 0 : 2;
+}

@@ -30,6 +30,9 @@
 // (hi, lo), the slot groups (s, kg) that hold a valid index, 8 halves each,
 // in slot order: one 16-byte load per lane gives a B fragment.
 #pragma once
+#include <cstddef>
+#include <type_traits>
+
 #include "dstd_common.h"
 #include "dstd_kernels.h"
 
@@ -299,6 +302,7 @@ struct TemporalHLArgs {
   const float* bf;
   const float* adjb;         // scale slot of the temporal conv_rm image (HLS_BOUND)
   int epi;                   // TemporalEpi: ENC, IN, RAW (C = 64); OUT, RAW (C = 3)
+  int pad_;                  // zero (explicit padding: bytewise comparison, see the chain launches)
   const float* xres;         // ENC: block input; OUT: model input [B][T][V][3]
   const float* bn_s;
   const float* bn_h;
@@ -334,6 +338,7 @@ struct AdjHLArgs {
   long out_sN, out_sG;      // halves
   int nchunk;               // column chunks per (sample, graph) workgroup set; 0: the launcher picks
                             // (more below one workgroup per CU: small batches)
+  int pad_;                 // zero (explicit padding)
 };
 
 struct TemporalFusedArgs {
@@ -350,6 +355,43 @@ struct BlockFusedArgs {
   AdjHLArgs s0;  // out != null (conv_st_in only): this block's own spatial planes from the model
                  // input (launch_adj_hl mode 0 args with xin), built before the spatial units
 };
+// The chain launches below accept a block by comparing whole argument structs
+// bytewise, so no byte of them is unnamed padding (the pad_ members, zero like
+// every member a builder leaves alone), and the kernels read them at fixed
+// places of the argument segment: sizes and offsets are pinned here.
+#define DSTD_OFFS_1(S, f, o) (offsetof(S, f) == o)
+#define DSTD_OFFS_4(S, f0, o0, f1, o1, f2, o2, f3, o3) \
+  (DSTD_OFFS_1(S, f0, o0) && DSTD_OFFS_1(S, f1, o1) && DSTD_OFFS_1(S, f2, o2) && DSTD_OFFS_1(S, f3, o3))
+#define DSTD_BYTEWISE(S, size) \
+  static_assert(std::has_unique_object_representations_v<S> && sizeof(S) == size, #S ": bytewise comparable, size pinned")
+DSTD_BYTEWISE(PQLayout, 24);
+static_assert(DSTD_OFFS_4(PQLayout, sn, 0, sch, 8, st, 12, sv, 16) && DSTD_OFFS_1(PQLayout, pad_, 20), "PQLayout");
+DSTD_BYTEWISE(SpatialHLArgs, 216);
+static_assert(DSTD_OFFS_4(SpatialHLArgs, x, 0, xmodel, 8, B, 12, T, 16) && DSTD_OFFS_4(SpatialHLArgs, V, 20, Cin, 24, Cout, 28, adj, 32) &&
+                  DSTD_OFFS_4(SpatialHLArgs, wimg, 40, wscale, 64, bf, 88, bn_s, 112) &&
+                  DSTD_OFFS_4(SpatialHLArgs, bn_h, 120, rbn_s, 128, rbn_h, 136, prelu, 144) &&
+                  DSTD_OFFS_4(SpatialHLArgs, adjb, 152, y, 168, pqimg, 176, pqscale, 184) &&
+                  DSTD_OFFS_1(SpatialHLArgs, pqb, 192) && DSTD_OFFS_1(SpatialHLArgs, pq, 208),
+              "SpatialHLArgs");
+DSTD_BYTEWISE(TemporalHLArgs, 168);
+static_assert(DSTD_OFFS_4(TemporalHLArgs, h, 0, B, 8, T, 12, V, 16) && DSTD_OFFS_4(TemporalHLArgs, C, 20, adj, 24, wimg, 32, wscale, 40) &&
+                  DSTD_OFFS_4(TemporalHLArgs, bf, 48, adjb, 56, epi, 64, pad_, 68) &&
+                  DSTD_OFFS_4(TemporalHLArgs, xres, 72, bn_s, 80, bn_h, 88, prelu, 96) &&
+                  DSTD_OFFS_4(TemporalHLArgs, y, 104, pqimg, 112, pqscale, 120, pqb, 128) && DSTD_OFFS_1(TemporalHLArgs, pq, 160),
+              "TemporalHLArgs");
+DSTD_BYTEWISE(AdjHLArgs, 224);
+static_assert(DSTD_OFFS_4(AdjHLArgs, xin, 0, mw, 8, mb, 40, pq, 72) && DSTD_OFFS_4(AdjHLArgs, pql, 80, p_ch, 104, B, 112, ngroups, 116) &&
+                  DSTD_OFFS_4(AdjHLArgs, wimg, 120, wscale, 136, bias, 152, alpha, 168) &&
+                  DSTD_OFFS_4(AdjHLArgs, astat, 176, out, 192, out_sN, 200, out_sG, 208) &&
+                  DSTD_OFFS_1(AdjHLArgs, nchunk, 216) && DSTD_OFFS_1(AdjHLArgs, pad_, 220),
+              "AdjHLArgs");
+DSTD_BYTEWISE(TemporalFusedArgs, 616);
+static_assert(DSTD_OFFS_1(TemporalFusedArgs, g, 0) && DSTD_OFFS_1(TemporalFusedArgs, j, 168) && DSTD_OFFS_1(TemporalFusedArgs, sn, 392),
+              "TemporalFusedArgs");
+DSTD_BYTEWISE(BlockFusedArgs, 1056);
+static_assert(DSTD_OFFS_1(BlockFusedArgs, s, 0) && DSTD_OFFS_1(BlockFusedArgs, t, 216) && DSTD_OFFS_1(BlockFusedArgs, s0, 832),
+              "BlockFusedArgs");
+#undef DSTD_BYTEWISE
 
 hipError_t launch_hl_prep(const HLPrepArgs& a, hipStream_t s);
 int hl_device_cus();  // compute units of the current device
@@ -393,6 +435,14 @@ hipError_t block_fused_args(const SpatialHLArgs& sa, const TemporalHLArgs& g, co
 // plane scratch and their layouts, which every encoder block shares) and, per
 // block, only what differs between encoder blocks: the activation buffers of
 // the rotation and the block's weight images, scales, biases and tables.
+//
+// The rule of both chain launches: a block's arguments are rebuilt from the
+// shared geometry and its descriptor by one set of host / device functions
+// (chain_block_* of dstd_hilo.hip), on the device by the kernels' accessors
+// and on the host by the appends, which accept a block only if the rebuild
+// gives back its BlockFusedArgs byte for byte.  A member that no descriptor
+// carries therefore equals the shared geometry's (or is zero where the rebuild
+// leaves it zero) in every block of a launch, with no list of such members.
 struct EncChainDesc {
   // spatial GC (SpatialHLArgs)
   const float* x;
@@ -441,61 +491,14 @@ struct EncChainArgs {
   EncChainDesc enc[kEncChainMax];
 };
 static_assert(sizeof(EncChainArgs) <= 4096, "kernel arguments end at 4 KB");
-// block i's arguments from the shared geometry and its descriptor
-__host__ __device__ inline void enc_chain_apply(const EncChainDesc& d, SpatialHLArgs& s) {
-  s.x = d.x;
-  s.y = d.h;
-  for (int g = 0; g < 2; ++g) {
-    s.wimg[g] = d.s_wimg[g];
-    s.wscale[g] = d.s_wscale[g];
-    s.bf[g] = d.s_bf[g];
-    s.adjb[g] = d.s_adjb[g];
-    s.pqb[g] = d.s_pqb[g];
-  }
-  s.bn_s = d.s_bn_s;
-  s.bn_h = d.s_bn_h;
-  s.prelu = d.s_prelu;
-  s.pqimg = d.s_pqimg;
-  s.pqscale = d.s_pqscale;
-}
-__host__ __device__ inline void enc_chain_apply(const EncChainDesc& d, TemporalHLArgs& g) {
-  g.h = d.h;
-  g.wimg = d.t_wimg;
-  g.wscale = d.t_wscale;
-  g.bf = d.t_bf;
-  g.adjb = d.t_adjb;
-  g.xres = d.t_xres;
-  g.bn_s = d.t_bn_s;
-  g.bn_h = d.t_bn_h;
-  g.prelu = d.t_prelu;
-  g.y = d.y;
-  g.pqimg = d.t_pqimg;
-  g.pqscale = d.t_pqscale;
-  for (int i = 0; i < 4; ++i) g.pqb[i] = d.t_pqb[i];
-}
-__host__ __device__ inline void enc_chain_apply_j(const EncChainDesc& d, AdjHLArgs& j) {
-  j.wimg[0] = d.j_wimg;
-  j.wscale[0] = d.j_wscale;
-  j.bias[0] = d.j_bias;
-  j.astat[0] = d.j_astat;
-  j.alpha = d.j_alpha;
-}
-__host__ __device__ inline void enc_chain_apply_sn(const EncChainDesc& d, AdjHLArgs& sn) {
-  for (int g = 0; g < 2; ++g) {
-    sn.wimg[g] = d.n_wimg[g];
-    sn.wscale[g] = d.n_wscale[g];
-    sn.bias[g] = d.n_bias[g];
-    sn.astat[g] = d.n_astat[g];
-  }
-  sn.alpha = d.n_alpha;
-}
 bool enc_chain_supported(int T, int V);
 // appends one validated encoder block (block_fused_args) to the run; the first
 // one sets the shared geometry.  hipErrorNotSupported when the block is no
-// 64 -> 64 ENC block with phase 3, differs from the run in anything but its
-// descriptor, or the run is full: the planner (dstd_plan.h) chooses runs that
-// pass, so to the caller a rejection is an error
+// 64 -> 64 ENC block with phase 3 on its own input, the rebuild of its place
+// in the run is not the block, or the run is full: the planner (dstd_plan.h)
+// chooses runs that pass, so to the caller a rejection is an error
 hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a);
+BlockFusedArgs enc_chain_block(const EncChainArgs& c, int b);  // block b of the run, rebuilt
 hipError_t launch_enc_chain(const EncChainArgs& c, hipStream_t s);
 
 // ---- the whole eval forward as one launch (k_model_chain) -----------------
@@ -535,65 +538,35 @@ struct ModelChainArgs {
   SpatialHLArgs s;      // shared geometry: the first encoder block's arguments
   TemporalFusedArgs t;
   int nenc;
-  int have;             // host only: 1 conv_st_in, 2 conv_st_out appended
   EncChainDesc enc[kModelChainMaxEnc];
   ModelEndDesc in, out;
   ModelAdj0Desc in0;
 };
 static_assert(sizeof(ModelChainArgs) + 256 <= 4096, "kernel arguments (with the hidden ones) end at 4 KB");
-__host__ __device__ inline void model_chain_apply_res(const ModelEndDesc& d, SpatialHLArgs& s) {
-  s.wimg[2] = d.s_wimg2;
-  s.wscale[2] = d.s_wscale2;
-  s.bf[2] = d.s_bf2;
-  s.rbn_s = d.s_rbn_s;
-  s.rbn_h = d.s_rbn_h;
-}
-__host__ __device__ inline void model_chain_apply_in(const ModelEndDesc& d, SpatialHLArgs& s) {
-  enc_chain_apply(d.e, s);
-  model_chain_apply_res(d, s);
-  s.xmodel = 1;
-  s.Cin = 6;
-}
-__host__ __device__ inline void model_chain_apply_in(const ModelEndDesc& d, TemporalHLArgs& g) {
-  enc_chain_apply(d.e, g);
-  g.epi = TEPI_IN;
-}
-__host__ __device__ inline void model_chain_apply_in0(const ModelAdj0Desc& d, AdjHLArgs& s0) {
-  s0.xin = d.xin;
-  for (int g = 0; g < 2; ++g) {
-    for (int i = 0; i < 2; ++i) {
-      s0.mw[g][i] = d.mw[g][i];
-      s0.mb[g][i] = d.mb[g][i];
-    }
-    s0.wimg[g] = d.wimg[g];
-    s0.wscale[g] = d.wscale[g];
-    s0.bias[g] = d.bias[g];
-    s0.astat[g] = d.astat[g];
-  }
-  s0.alpha = d.alpha;
-}
-__host__ __device__ inline void model_chain_apply_out(const ModelEndDesc& d, SpatialHLArgs& s) {
-  enc_chain_apply(d.e, s);
-  model_chain_apply_res(d, s);
-  s.Cout = 3;
-}
-__host__ __device__ inline void model_chain_apply_out(const ModelEndDesc& d, TemporalHLArgs& g) {
-  enc_chain_apply(d.e, g);
-  g.C = 3;
-  g.epi = TEPI_OUT;
-  g.pq = nullptr;
-}
+static_assert(sizeof(EncChainArgs) == 3784 && DSTD_OFFS_4(EncChainArgs, s, 0, t, 216, nblk, 832, enc, 840) &&
+                  sizeof(ModelChainArgs) == 3640 && DSTD_OFFS_4(ModelChainArgs, s, 0, t, 216, nenc, 832, enc, 840) &&
+                  DSTD_OFFS_1(ModelChainArgs, in, 2680) && DSTD_OFFS_1(ModelChainArgs, out, 3088) &&
+                  DSTD_OFFS_1(ModelChainArgs, in0, 3496),
+              "the chain kernels' argument segments");
+#undef DSTD_OFFS_4
+#undef DSTD_OFFS_1
+// the launch being filled, on the host
+struct ModelChain {
+  ModelChainArgs a;
+  int have;  // 1 conv_st_in, 2 conv_st_out appended
+};
+enum ChainKind { CHAIN_IN = 0, CHAIN_ENC = 1, CHAIN_OUT = 2 };  // a block's kind: conv_st_in, encoder block b, conv_st_out
 bool model_chain_supported(int T, int V);
 // appends the forward's next block (block_fused_args): the encoder blocks
 // first (1..kModelChainMaxEnc, as enc_chain_append: the first one sets the
 // shared geometry), then conv_st_in (with s0) and conv_st_out in either order.
-// hipErrorNotSupported when the block is none of the three kinds, differs from
-// the shared geometry in anything outside its compact form, or its place is
-// taken (an error to the caller, as for enc_chain_append)
-hipError_t model_chain_append(ModelChainArgs* c, const BlockFusedArgs& a);
+// hipErrorNotSupported when the block is none of the three kinds, the rebuild
+// of its place is not the block, or its place is taken (an error to the
+// caller, as for enc_chain_append)
+hipError_t model_chain_append(ModelChain* c, const BlockFusedArgs& a);
+BlockFusedArgs model_chain_block(const ModelChainArgs& c, int kind, int b);  // the block of kind (b: CHAIN_ENC), rebuilt
 // conv_st_in, at least one encoder block and conv_st_out are in place
-bool model_chain_complete(const ModelChainArgs& c);
-hipError_t launch_model_chain(const ModelChainArgs& c, hipStream_t s);
-
+bool model_chain_complete(const ModelChain& c);
+hipError_t launch_model_chain(const ModelChain& c, hipStream_t s);
 
 }  // namespace dstd

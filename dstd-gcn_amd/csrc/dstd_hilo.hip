@@ -20,6 +20,8 @@
 //    epilogue, stores are 16 bytes per lane.
 // Weights come as fragment images (k_hl_prep) copied into LDS with 16-byte
 // loads.  Units are contiguous ranges per wave, no barrier after the prologue.
+#include <string.h>
+
 #include <type_traits>
 
 #include "dstd_common.h"
@@ -2155,8 +2157,8 @@ template <int T, int V>
 constexpr int tf_waves() { return T == 35 && V == 22 ? kTfWavesH36M : 8; }
 
 // How the fused bodies get at their arguments: accessors called where a phase
-// begins.  Here the launch's own argument structs; k_enc_chain's block b:
-// EncChainArgsAt below.
+// begins.  Here the launch's own argument structs; a chain launch's block b:
+// ChainArgsAt below.
 struct BlockArgsRef {
   const SpatialHLArgs* s_;
   const TemporalFusedArgs* t_;
@@ -2701,53 +2703,177 @@ __global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_wave
   block_fused_body<T, V, CIN, COUT, EPI>(BlockArgsRef{&ba.s, &ba.t, &ba.s0}, blockIdx.x, dsm, threadIdx.x);  // one sample per workgroup
 }
 
-// Block b of a run: each accessor re-reads what its phase needs from the
-// kernel-argument segment through an opaque copy of the segment pointer, so
-// the loads stay in the phase that uses them (as k_block_fused's own argument
-// loads do) -- seen as loop invariants they would be hoisted out of the block
-// loop into SGPRs held through all four phases
-struct EncChainArgsAt {
+// ---- block b of kind PH of a chain launch, from the launch's arguments -----
+// One function per accessor of the fused body (spatial, temporal g, j, sn,
+// s0).  p points at the launch's EncChainArgs (CHAIN_ENC only) or
+// ModelChainArgs: the kernel-argument segment on the device, the struct being
+// filled on the host.  Each reads the shared geometry and the block's
+// descriptor by value and sets what the descriptor carries and what the kind
+// fixes.
+template <typename S, typename P>
+__host__ __device__ __forceinline__ S chain_get(P p) {
+  S r;
+  __builtin_memcpy(&r, p, sizeof(S));
+  return r;
+}
+// the kind's descriptor, and the encoder descriptor inside it (chain_enc_part)
+template <int PH, typename P>
+__host__ __device__ __forceinline__ auto chain_desc(P p, int b) {
+  if constexpr (PH == CHAIN_IN) return chain_get<ModelEndDesc>(&p->in);
+  else if constexpr (PH == CHAIN_ENC) return chain_get<EncChainDesc>(&p->enc[b]);
+  else return chain_get<ModelEndDesc>(&p->out);
+}
+__host__ __device__ __forceinline__ const EncChainDesc& chain_enc_part(const EncChainDesc& d) { return d; }
+__host__ __device__ __forceinline__ const EncChainDesc& chain_enc_part(const ModelEndDesc& d) { return d.e; }
+// (S: SpatialHLArgs or the kernels' register copy of it)
+template <int PH, typename S = SpatialHLArgs, typename P>
+__host__ __device__ __forceinline__ S chain_block_s(P p, int b) {
+  S s = chain_get<S>(&p->s);
+  const auto dd = chain_desc<PH>(p, b);
+  const EncChainDesc& d = chain_enc_part(dd);
+  s.x = d.x;
+  s.y = d.h;
+  for (int g = 0; g < 2; ++g) {
+    s.wimg[g] = d.s_wimg[g];
+    s.wscale[g] = d.s_wscale[g];
+    s.bf[g] = d.s_bf[g];
+    s.adjb[g] = d.s_adjb[g];
+    s.pqb[g] = d.s_pqb[g];
+  }
+  s.bn_s = d.s_bn_s;
+  s.bn_h = d.s_bn_h;
+  s.prelu = d.s_prelu;
+  s.pqimg = d.s_pqimg;
+  s.pqscale = d.s_pqscale;
+  if constexpr (PH != CHAIN_ENC) {  // the residual conv and its folded BN; 6 -> 64 from the model input, 64 -> 3
+    s.wimg[2] = dd.s_wimg2;
+    s.wscale[2] = dd.s_wscale2;
+    s.bf[2] = dd.s_bf2;
+    s.rbn_s = dd.s_rbn_s;
+    s.rbn_h = dd.s_rbn_h;
+    if constexpr (PH == CHAIN_IN) {
+      s.xmodel = 1;
+      s.Cin = 6;
+    } else {
+      s.Cout = 3;
+    }
+  }
+  return s;
+}
+template <int PH, typename P>
+__host__ __device__ __forceinline__ TemporalHLArgs chain_block_g(P p, int b) {
+  TemporalHLArgs g = chain_get<TemporalHLArgs>(&p->t.g);
+  const auto dd = chain_desc<PH>(p, b);
+  const EncChainDesc& d = chain_enc_part(dd);
+  g.h = d.h;
+  g.wimg = d.t_wimg;
+  g.wscale = d.t_wscale;
+  g.bf = d.t_bf;
+  g.adjb = d.t_adjb;
+  g.xres = d.t_xres;
+  g.bn_s = d.t_bn_s;
+  g.bn_h = d.t_bn_h;
+  g.prelu = d.t_prelu;
+  g.y = d.y;
+  g.pqimg = d.t_pqimg;
+  g.pqscale = d.t_pqscale;
+  for (int i = 0; i < 4; ++i) g.pqb[i] = d.t_pqb[i];
+  if constexpr (PH == CHAIN_IN) g.epi = TEPI_IN;
+  if constexpr (PH == CHAIN_OUT) {  // no P/Q conv: no block follows
+    g.C = 3;
+    g.epi = TEPI_OUT;
+    g.pq = nullptr;
+  }
+  return g;
+}
+template <int PH, typename P>
+__host__ __device__ __forceinline__ AdjHLArgs chain_block_j(P p, int b) {
+  AdjHLArgs j = chain_get<AdjHLArgs>(&p->t.j);
+  const auto dd = chain_desc<PH>(p, b);
+  const EncChainDesc& d = chain_enc_part(dd);
+  j.wimg[0] = d.j_wimg;
+  j.wscale[0] = d.j_wscale;
+  j.bias[0] = d.j_bias;
+  j.astat[0] = d.j_astat;
+  j.alpha = d.j_alpha;
+  return j;
+}
+template <int PH, typename P>
+__host__ __device__ __forceinline__ AdjHLArgs chain_block_sn(P p, int b) {
+  if constexpr (PH == CHAIN_OUT) return AdjHLArgs{};  // no phase 3 (C == 3)
+  else {
+    AdjHLArgs sn = chain_get<AdjHLArgs>(&p->t.sn);
+    const auto dd = chain_desc<PH>(p, b);
+  const EncChainDesc& d = chain_enc_part(dd);
+    for (int g = 0; g < 2; ++g) {
+      sn.wimg[g] = d.n_wimg[g];
+      sn.wscale[g] = d.n_wscale[g];
+      sn.bias[g] = d.n_bias[g];
+      sn.astat[g] = d.n_astat[g];
+    }
+    sn.alpha = d.n_alpha;
+    return sn;
+  }
+}
+// conv_st_in: the shared sn's layout and planes, its own inputs
+template <int PH, typename P>
+__host__ __device__ __forceinline__ AdjHLArgs chain_block_s0(P p, int) {
+  if constexpr (PH != CHAIN_IN) return AdjHLArgs{};
+  else {
+    AdjHLArgs s0 = chain_get<AdjHLArgs>(&p->t.sn);
+    const ModelAdj0Desc d = chain_get<ModelAdj0Desc>(&p->in0);
+    s0.xin = d.xin;
+    for (int g = 0; g < 2; ++g) {
+      for (int i = 0; i < 2; ++i) {
+        s0.mw[g][i] = d.mw[g][i];
+        s0.mb[g][i] = d.mb[g][i];
+      }
+      s0.wimg[g] = d.wimg[g];
+      s0.wscale[g] = d.wscale[g];
+      s0.bias[g] = d.bias[g];
+      s0.astat[g] = d.astat[g];
+    }
+    s0.alpha = d.alpha;
+    return s0;
+  }
+}
+
+// Block b of kind PH (ChainKind) of a chain launch whose only argument is an A
+// (EncChainArgs: a run of encoder blocks; ModelChainArgs: the whole forward):
+// each accessor re-reads what its phase needs from the kernel-argument segment
+// through an opaque copy of the segment pointer, so the loads stay in the
+// phase that uses them (as k_block_fused's own argument loads do) -- seen as
+// loop invariants they would be hoisted out of the block loop into SGPRs held
+// through all four phases.  What they read: chain_block_* above, which the
+// host ran on the same arguments when it accepted the block.
+template <typename A, int PH>
+struct ChainArgsAt {
   int b;
-  typedef const EncChainArgs __attribute__((address_space(4))) * KP;
+  typedef const A __attribute__((address_space(4))) * KP;
   __device__ __forceinline__ KP base() const {
-    KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();  // EncChainArgs is k_enc_chain's only argument
+    KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();  // A is the kernel's only argument
     asm volatile("" : "+s"(p));
     return p;
   }
-  template <typename S, typename P>
-  __device__ __forceinline__ static S get(P p) {
-    S r;
-    __builtin_memcpy(&r, p, sizeof(S));
-    return r;
-  }
-  __device__ __forceinline__ SpatialHLArgsVal s() const {
-    KP p = base();
-    SpatialHLArgsVal r = get<SpatialHLArgsVal>(&p->s);
-    enc_chain_apply(get<EncChainDesc>(&p->enc[b]), r);
-    return r;
-  }
-  __device__ __forceinline__ TemporalHLArgs tg() const {
-    KP p = base();
-    TemporalHLArgs r = get<TemporalHLArgs>(&p->t.g);
-    enc_chain_apply(get<EncChainDesc>(&p->enc[b]), r);
-    return r;
-  }
-  __device__ __forceinline__ AdjHLArgs tj() const {
-    KP p = base();
-    AdjHLArgs r = get<AdjHLArgs>(&p->t.j);
-    enc_chain_apply_j(get<EncChainDesc>(&p->enc[b]), r);
-    return r;
-  }
-  __device__ __forceinline__ AdjHLArgs tsn() const {
-    KP p = base();
-    AdjHLArgs r = get<AdjHLArgs>(&p->t.sn);
-    enc_chain_apply_sn(get<EncChainDesc>(&p->enc[b]), r);
-    return r;
-  }
-  __device__ __forceinline__ AdjHLArgs s0() const { return AdjHLArgs{}; }  // (conv_st_in only)
-  // (a constant zero vector is hoisted out of the block loop and spilled)
-  __device__ __forceinline__ static uint32_t zero() { return (uint32_t)opaque_zero(); }
+  __device__ __forceinline__ SpatialHLArgsVal s() const { return chain_block_s<PH, SpatialHLArgsVal>(base(), b); }
+  __device__ __forceinline__ TemporalHLArgs tg() const { return chain_block_g<PH>(base(), b); }
+  __device__ __forceinline__ AdjHLArgs tj() const { return chain_block_j<PH>(base(), b); }
+  __device__ __forceinline__ AdjHLArgs tsn() const { return chain_block_sn<PH>(base(), b); }
+  __device__ __forceinline__ AdjHLArgs s0() const { return chain_block_s0<PH>(base(), b); }
+  // (a constant zero vector is hoisted out of the block loop and spilled;
+  // conv_st_in is in no loop and takes the plain one, as k_block_fused does)
+  __device__ __forceinline__ static uint32_t zero() { return PH == CHAIN_IN ? 0u : (uint32_t)opaque_zero(); }
 };
+
+#define DSTD_CHAIN_OPAQUE_IDS                      \
+  int tid = threadIdx.x, n = blockIdx.x, lds0 = 0; \
+  asm volatile("" : "+v"(tid));                    \
+  asm volatile("" : "+s"(n), "+s"(lds0));
+// the run's block boundary (k_enc_chain): every wave's stores and LDS accesses
+// complete, then the workgroup meets
+#define DSTD_CHAIN_BOUNDARY          \
+  __builtin_amdgcn_s_waitcnt(0);     \
+  __syncthreads();
 
 // ===========================================================================
 // A run of consecutive encoder blocks in one launch: the workgroup of
@@ -2769,10 +2895,8 @@ __global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_wave
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
 #pragma nounroll
   for (int b = 0; b < ca.nblk; ++b) {
-    int tid = threadIdx.x, n = blockIdx.x, lds0 = 0;
-    asm volatile("" : "+v"(tid));
-    asm volatile("" : "+s"(n), "+s"(lds0));
-    block_fused_body<T, V, 64, 64, TEPI_ENC>(EncChainArgsAt{b}, n, dsm + lds0, tid);
+    DSTD_CHAIN_OPAQUE_IDS
+    block_fused_body<T, V, 64, 64, TEPI_ENC>(ChainArgsAt<EncChainArgs, CHAIN_ENC>{b}, n, dsm + lds0, tid);
     // Block boundary.  What a kernel end gave the per-block schedule, the
     // run provides itself: every wave waits until its own stores (y, the
     // next block's spatial P/Q and planes) and LDS accesses are complete,
@@ -2790,71 +2914,9 @@ __global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_wave
     // All of it is sample n's slice, written and read by this workgroup alone
     // through the CU's own L1 (workgroup scope, as between the phases of one
     // block).
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
+    DSTD_CHAIN_BOUNDARY
   }
 }
-
-// Block PH of the whole forward (0 conv_st_in, 1 encoder block b, 2
-// conv_st_out): EncChainArgsAt's accessors over ModelChainArgs, the end blocks
-// through their compact forms.
-template <int PH>
-struct ModelChainArgsAt {
-  int b;
-  typedef const ModelChainArgs __attribute__((address_space(4))) * KP;
-  __device__ __forceinline__ KP base() const {
-    KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();  // ModelChainArgs is k_model_chain's only argument
-    asm volatile("" : "+s"(p));
-    return p;
-  }
-  template <typename S, typename P>
-  __device__ __forceinline__ static S get(P p) {
-    S r;
-    __builtin_memcpy(&r, p, sizeof(S));
-    return r;
-  }
-  __device__ __forceinline__ SpatialHLArgsVal s() const {
-    KP p = base();
-    SpatialHLArgsVal r = get<SpatialHLArgsVal>(&p->s);
-    if constexpr (PH == 0) model_chain_apply_in(get<ModelEndDesc>(&p->in), r);
-    else if constexpr (PH == 1) enc_chain_apply(get<EncChainDesc>(&p->enc[b]), r);
-    else model_chain_apply_out(get<ModelEndDesc>(&p->out), r);
-    return r;
-  }
-  __device__ __forceinline__ TemporalHLArgs tg() const {
-    KP p = base();
-    TemporalHLArgs r = get<TemporalHLArgs>(&p->t.g);
-    if constexpr (PH == 0) model_chain_apply_in(get<ModelEndDesc>(&p->in), r);
-    else if constexpr (PH == 1) enc_chain_apply(get<EncChainDesc>(&p->enc[b]), r);
-    else model_chain_apply_out(get<ModelEndDesc>(&p->out), r);
-    return r;
-  }
-  __device__ __forceinline__ EncChainDesc desc(KP p) const {
-    if constexpr (PH == 0) return get<EncChainDesc>(&p->in.e);
-    else if constexpr (PH == 1) return get<EncChainDesc>(&p->enc[b]);
-    else return get<EncChainDesc>(&p->out.e);
-  }
-  __device__ __forceinline__ AdjHLArgs tj() const {
-    KP p = base();
-    AdjHLArgs r = get<AdjHLArgs>(&p->t.j);
-    enc_chain_apply_j(desc(p), r);
-    return r;
-  }
-  __device__ __forceinline__ AdjHLArgs tsn() const {  // (conv_st_out has no phase 3: C == 3)
-    KP p = base();
-    AdjHLArgs r = get<AdjHLArgs>(&p->t.sn);
-    enc_chain_apply_sn(desc(p), r);
-    return r;
-  }
-  __device__ __forceinline__ AdjHLArgs s0() const {  // conv_st_in: the shared sn's layout and planes, its own inputs
-    if constexpr (PH != 0) return AdjHLArgs{};
-    KP p = base();
-    AdjHLArgs r = get<AdjHLArgs>(&p->t.sn);
-    model_chain_apply_in0(get<ModelAdj0Desc>(&p->in0), r);
-    return r;
-  }
-  __device__ __forceinline__ static uint32_t zero() { return PH == 0 ? 0u : (uint32_t)opaque_zero(); }
-};
 
 // ===========================================================================
 // The whole eval forward in one launch: the workgroup of k_enc_chain runs
@@ -2875,16 +2937,6 @@ struct ModelChainGeom {
   static constexpr size_t LDS = LI > LE ? (LI > LO ? LI : LO) : (LE > LO ? LE : LO);
 };
 
-#define DSTD_CHAIN_OPAQUE_IDS                      \
-  int tid = threadIdx.x, n = blockIdx.x, lds0 = 0; \
-  asm volatile("" : "+v"(tid));                    \
-  asm volatile("" : "+s"(n), "+s"(lds0));
-// the run's block boundary (k_enc_chain): every wave's stores and LDS accesses
-// complete, then the workgroup meets
-#define DSTD_CHAIN_BOUNDARY          \
-  __builtin_amdgcn_s_waitcnt(0);     \
-  __syncthreads();
-
 template <int T, int V>
 __global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_waves_per_eu((tf_waves<T, V>() / 4), (tf_waves<T, V>() / 4)))) void k_model_chain(ModelChainArgs ca) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
@@ -2903,7 +2955,7 @@ __global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_wave
     // an opaque tid beside threadIdx.x, which the later bodies keep live (8
     // VGPR spills at H36M).  Nothing derived from them can be shared with the
     // later bodies, whose copies are opaque, and this body is in no loop.
-    block_fused_body<T, V, 6, 64, TEPI_IN>(ModelChainArgsAt<0>{0}, blockIdx.x, dsm, threadIdx.x);
+    block_fused_body<T, V, 6, 64, TEPI_IN>(ChainArgsAt<ModelChainArgs, CHAIN_IN>{0}, blockIdx.x, dsm, threadIdx.x);
     // as between encoder blocks (k_enc_chain); conv_st_in's y, temporal P/Q
     // and phase-3 planes are what the first encoder block reads
     DSTD_CHAIN_BOUNDARY
@@ -2911,12 +2963,12 @@ __global__ __launch_bounds__((64 * tf_waves<T, V>())) __attribute__((amdgpu_wave
 #pragma nounroll
   for (int b = 0; b < ca.nenc; ++b) {
     DSTD_CHAIN_OPAQUE_IDS
-    block_fused_body<T, V, 64, 64, TEPI_ENC>(ModelChainArgsAt<1>{b}, n, dsm + lds0, tid);
+    block_fused_body<T, V, 64, 64, TEPI_ENC>(ChainArgsAt<ModelChainArgs, CHAIN_ENC>{b}, n, dsm + lds0, tid);
     DSTD_CHAIN_BOUNDARY
   }
   {
     DSTD_CHAIN_OPAQUE_IDS
-    block_fused_body<T, V, 64, 3, TEPI_OUT>(ModelChainArgsAt<2>{0}, n, dsm + lds0, tid);
+    block_fused_body<T, V, 64, 3, TEPI_OUT>(ChainArgsAt<ModelChainArgs, CHAIN_OUT>{0}, n, dsm + lds0, tid);
   }
 }
 #undef DSTD_CHAIN_OPAQUE_IDS
@@ -2955,6 +3007,61 @@ hipError_t launch_units(int units, const A& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// The split-f16 shapes (T frames, V joints): those whose adjacency kernels
+// (dstd_adj.hip) have a split-f16 writer.  Every (T, V) dispatch and shape
+// predicate below reads this table.
+struct HLShape {
+  int T, V;
+};
+constexpr HLShape kHLShapes[] = {{35, 22}, {35, 25}, {40, 23}, {75, 22}};
+constexpr int kNumHLShapes = sizeof(kHLShapes) / sizeof(kHLShapes[0]);
+template <int I>
+struct HLShapeAt {
+  static constexpr int T = kHLShapes[I].T, V = kHLShapes[I].V;
+  // a whole block per workgroup (k_block_fused, the chains): where the fused
+  // temporal GC runs every output frame in one chunk (not T = 75)
+  static constexpr bool block = !TFusedGeom<T, V, TEPI_ENC, 64>::UCH;
+};
+// f(HLShapeAt<I>{}) at the table's entry (T, V); hipErrorNotSupported off the table
+template <int I = 0, typename F>
+hipError_t hl_dispatch(int T, int V, const F& f) {
+  if constexpr (I == kNumHLShapes) return hipErrorNotSupported;
+  else return T == HLShapeAt<I>::T && V == HLShapeAt<I>::V ? f(HLShapeAt<I>{}) : hl_dispatch<I + 1>(T, V, f);
+}
+// (T, V) is in the table and pred(HLShapeAt<I>{}) holds there
+template <typename F>
+bool hl_shape_is(int T, int V, const F& pred) {
+  return hl_dispatch(T, V, [&](auto sh) { return pred(sh) ? hipSuccess : hipErrorNotSupported; }) == hipSuccess;
+}
+bool hl_shape(int T, int V) {
+  return hl_shape_is(T, V, [](auto) { return true; });
+}
+// hl_dispatch over the shapes that run a whole block per workgroup
+template <typename F>
+hipError_t hl_dispatch_block(int T, int V, const F& f) {
+  return hl_dispatch(T, V, [&](auto sh) {
+    if constexpr (decltype(sh)::block) return f(sh);
+    else return hipErrorNotSupported;
+  });
+}
+// some shape of the table at T takes the temporal GC's residual in the accumulator
+constexpr bool hl_res_acc_at(int T) {
+  for (const HLShape& sh : kHLShapes)
+    if (sh.T == T && tf_res_acc(T, sh.V)) return true;
+  return false;
+}
+
+// One workgroup per sample of K, a per-sample kernel's instantiation at (T, V)
+// (k_temporal_fused, k_block_fused, the chains), on LDS bytes of dynamic LDS.
+template <auto K, int T, int V, size_t LDS, typename A>
+hipError_t launch_per_sample(int B, const A& a, hipStream_t s) {
+  static const hipError_t attr =
+      hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);  // one per kernel instantiation
+  if (attr != hipSuccess) return attr;
+  hipLaunchKernelGGL(K, dim3(B), dim3(64 * tf_waves<T, V>()), LDS, s, a);
+  return hipGetLastError();
+}
+
 template <int T>
 hipError_t temporal_hl_t(const TemporalHLArgs& a, hipStream_t s) {
   if (a.C == 3) {
@@ -2968,11 +3075,8 @@ hipError_t temporal_hl_t(const TemporalHLArgs& a, hipStream_t s) {
   if (a.C != 64) return hipErrorNotSupported;
   switch (a.epi) {
     case TEPI_ENC:
-      if constexpr (tf_res_acc(T, 25)) {
-        if (a.V == 25) return launch_units<k_temporal_hl<T, TEPI_ENC, 64, true>, temporal_nt<T, 64>()>(a.B * a.V, a, s);
-      }
-      if constexpr (tf_res_acc(T, 23)) {
-        if (a.V == 23) return launch_units<k_temporal_hl<T, TEPI_ENC, 64, true>, temporal_nt<T, 64>()>(a.B * a.V, a, s);
+      if constexpr (hl_res_acc_at(T)) {
+        if (tf_res_acc(T, a.V)) return launch_units<k_temporal_hl<T, TEPI_ENC, 64, true>, temporal_nt<T, 64>()>(a.B * a.V, a, s);
       }
       return launch_units<k_temporal_hl<T, TEPI_ENC, 64>, temporal_nt<T, 64>()>(a.B * a.V, a, s);
     case TEPI_IN: return launch_units<k_temporal_hl<T, TEPI_IN, 64>, temporal_nt<T, 64>()>(a.B * a.V, a, s);
@@ -2992,10 +3096,6 @@ hipError_t launch_hl_prep(const HLPrepArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// the shapes whose adjacency kernels (dstd_adj.hip) have a split-f16 writer
-static bool hl_shape(int T, int V) {
-  return (T == 35 && (V == 22 || V == 25)) || (T == 40 && V == 23) || (T == 75 && V == 22);
-}
 bool spatial_hl_supported(int T, int V) { return hl_shape(T, V); }
 
 template <int MODE, int NROW, int K, int NA>
@@ -3023,18 +3123,8 @@ hipError_t launch_adj_hl(const AdjHLArgs& a, int mode, int T, int V, hipStream_t
     return hipErrorNotSupported;
   for (int g = 0; g < a.ngroups; ++g)
     if (a.p_ch[g] & 3) return hipErrorNotSupported;
-  if (mode == 0) {
-    if (T == 35 && V == 22) return adj_hl_run<0, 35, 70, 22>(a, s);
-    if (T == 35 && V == 25) return adj_hl_run<0, 35, 70, 25>(a, s);
-    if (T == 40 && V == 23) return adj_hl_run<0, 40, 80, 23>(a, s);
-    if (T == 75 && V == 22) return adj_hl_run<0, 75, 150, 22>(a, s);
-  } else {
-    if (T == 35 && V == 22) return adj_hl_run<1, 22, 44, 35>(a, s);
-    if (T == 35 && V == 25) return adj_hl_run<1, 25, 50, 35>(a, s);
-    if (T == 40 && V == 23) return adj_hl_run<1, 23, 46, 40>(a, s);
-    if (T == 75 && V == 22) return adj_hl_run<1, 22, 44, 75>(a, s);
-  }
-  return hipErrorNotSupported;
+  if (mode == 0) return hl_dispatch(T, V, [&](auto sh) { return adj_hl_run<0, decltype(sh)::T, 2 * decltype(sh)::T, decltype(sh)::V>(a, s); });
+  return hl_dispatch(T, V, [&](auto sh) { return adj_hl_run<1, decltype(sh)::V, 2 * decltype(sh)::V, decltype(sh)::T>(a, s); });
 }
 bool temporal_hl_supported(int T, int V) { return hl_shape(T, V); }
 
@@ -3058,12 +3148,7 @@ hipError_t launch_spatial_hl(const SpatialHLArgs& a, hipStream_t s) {
 
 template <int T, int V, int EPI, int C>
 hipError_t tfused_run(const TemporalFusedArgs& a, hipStream_t s) {
-  using Gm = TFusedGeom<T, V, EPI, C>;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)k_temporal_fused<T, V, EPI, C>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::LDS);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((k_temporal_fused<T, V, EPI, C>), dim3(a.g.B), dim3(64 * tf_waves<T, V>()), Gm::LDS, s, a);
-  return hipGetLastError();
+  return launch_per_sample<k_temporal_fused<T, V, EPI, C>, T, V, TFusedGeom<T, V, EPI, C>::LDS>(a.g.B, a, s);
 }
 
 template <int T, int V>
@@ -3087,12 +3172,7 @@ hipError_t tfused_tv(const TemporalFusedArgs& a, hipStream_t s) {
 
 template <int T, int V, int CIN, int COUT, int EPI>
 hipError_t bfused_run(const BlockFusedArgs& a, hipStream_t s) {
-  using Gm = BlockFusedGeom<T, V, CIN, COUT, EPI>;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)k_block_fused<T, V, CIN, COUT, EPI>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::LDS);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((k_block_fused<T, V, CIN, COUT, EPI>), dim3(a.t.g.B), dim3(64 * tf_waves<T, V>()), Gm::LDS, s, a);
-  return hipGetLastError();
+  return launch_per_sample<k_block_fused<T, V, CIN, COUT, EPI>, T, V, BlockFusedGeom<T, V, CIN, COUT, EPI>::LDS>(a.t.g.B, a, s);
 }
 
 // the model's three block kinds: conv_st_in (6 -> 64, IN tail), encoders
@@ -3106,10 +3186,15 @@ hipError_t bfused_tv(const BlockFusedArgs& a, hipStream_t s) {
   return hipErrorNotSupported;
 }
 
+// the block kind (ChainKind) of (Cin, Cout, epilogue); -1: none of the model's three
+static int block_kind(int cin, int cout, int epi) {
+  if (cin == 64 && cout == 64 && epi == TEPI_ENC) return CHAIN_ENC;
+  if (cin == 6 && cout == 64 && epi == TEPI_IN) return CHAIN_IN;
+  if (cin == 64 && cout == 3 && epi == TEPI_OUT) return CHAIN_OUT;
+  return -1;
+}
 bool block_fused_supported(int T, int V, int cin, int cout, int epi) {
-  const bool shape = (T == 35 && (V == 22 || V == 25)) || (T == 40 && V == 23);
-  return shape && ((cin == 64 && cout == 64 && epi == TEPI_ENC) || (cin == 6 && cout == 64 && epi == TEPI_IN) ||
-                   (cin == 64 && cout == 3 && epi == TEPI_OUT));
+  return block_kind(cin, cout, epi) >= 0 && hl_shape_is(T, V, [](auto sh) { return decltype(sh)::block; });
 }
 
 bool block_fused_adj0_supported(int T, int V) {
@@ -3145,59 +3230,43 @@ hipError_t launch_block_fused(const SpatialHLArgs& sa, const TemporalHLArgs& g, 
   BlockFusedArgs a;
   const hipError_t e = block_fused_args(sa, g, j, sn, &a, s0);
   if (e != hipSuccess) return e;
-  if (g.T == 35 && g.V == 22) return bfused_tv<35, 22>(a, s);
-  if (g.T == 35 && g.V == 25) return bfused_tv<35, 25>(a, s);
-  if (g.T == 40 && g.V == 23) return bfused_tv<40, 23>(a, s);
-  return hipErrorNotSupported;
+  return hl_dispatch_block(g.T, g.V, [&](auto sh) { return bfused_tv<decltype(sh)::T, decltype(sh)::V>(a, s); });
 }
 
 bool enc_chain_supported(int T, int V) { return block_fused_supported(T, V, 64, 64, TEPI_ENC) && temporal_fused_phase3(T, V); }
+bool model_chain_supported(int T, int V) {
+  return enc_chain_supported(T, V) && block_fused_adj0_supported(T, V) && block_fused_supported(T, V, 64, 3, TEPI_OUT);
+}
 
-// a 64 -> 64 ENC block with phase 3, as a run takes it
-static bool enc_chain_kind_ok(const BlockFusedArgs& a) {
+// What the rebuild cannot show -- the first encoder block IS the shared
+// geometry, so its own rebuild is trivially equal: the block is of kind k at a
+// supported shape and has what only that kind's body dereferences.
+static bool chain_kind_ok(int k, const BlockFusedArgs& a) {
   const SpatialHLArgs& s = a.s;
   const TemporalHLArgs& g = a.t.g;
-  const AdjHLArgs &j = a.t.j, &n = a.t.sn;
-  return enc_chain_supported(g.T, g.V) && s.Cin == 64 && s.Cout == 64 && g.epi == TEPI_ENC && !s.xmodel && n.out &&
-         !a.s0.out && g.xres == s.x && !s.wimg[2] && !s.wscale[2] && !s.bf[2] && !s.rbn_s && !s.rbn_h && !j.xin && !n.xin;
-}
-// what an adjacency's arguments share over a run: everything but its weight
-// images, scales, biases, tables and (conv_st_in's s0) model-input fields
-static bool chain_same_adj(const AdjHLArgs& p, const AdjHLArgs& q) {
-  return p.pq == q.pq && p.pql.sn == q.pql.sn && p.pql.st == q.pql.st && p.pql.sv == q.pql.sv &&
-         p.pql.sch == q.pql.sch && p.p_ch[0] == q.p_ch[0] && p.p_ch[1] == q.p_ch[1] && p.B == q.B &&
-         p.ngroups == q.ngroups && p.out == q.out && p.out_sN == q.out_sN && p.out_sG == q.out_sG &&
-         p.nchunk == q.nchunk;
-}
-// an encoder block's arguments outside its descriptor equal the shared geometry (s0, t0)
-static bool enc_chain_same_geometry(const BlockFusedArgs& a, const SpatialHLArgs& s0, const TemporalFusedArgs& t0) {
-  const SpatialHLArgs& s = a.s;
-  const TemporalHLArgs &g = a.t.g, &g0 = t0.g;
-  return s.B == s0.B && s.T == s0.T && s.V == s0.V && s.adj == s0.adj && s.pq == s0.pq && g.B == g0.B && g.T == g0.T &&
-         g.V == g0.V && g.C == g0.C && g.adj == g0.adj && g.pq == g0.pq && chain_same_adj(a.t.j, t0.j) &&
-         chain_same_adj(a.t.sn, t0.sn);
-}
-static EncChainDesc enc_chain_desc(const BlockFusedArgs& a);
-
-// One more encoder block for a launch that carries the shared geometry (s, t:
-// the first block's arguments) and a descriptor per block (enc[0..n) of cap):
-// k_enc_chain's run and k_model_chain's encoder stack alike.
-static hipError_t chain_append_enc(SpatialHLArgs& s, TemporalFusedArgs& t, EncChainDesc* enc, int& n, int cap,
-                                   const BlockFusedArgs& a) {
-  if (n >= cap || !enc_chain_kind_ok(a)) return hipErrorNotSupported;
-  if (n == 0) {
-    s = a.s;
-    t = a.t;
-  } else if (!enc_chain_same_geometry(a, s, t)) {
-    return hipErrorNotSupported;
-  }
-  enc[n++] = enc_chain_desc(a);
-  return hipSuccess;
+  if (k < 0 || k != block_kind(s.Cin, s.Cout, g.epi)) return false;
+  // an encoder block: phase 3; its residual is its own input, not the model's
+  if (k == CHAIN_ENC) return enc_chain_supported(g.T, g.V) && a.t.sn.out && g.xres == s.x && !s.xmodel;
+  // an end block: the residual conv and its folded BN
+  if (!model_chain_supported(g.T, g.V) || !s.wimg[2] || !s.wscale[2] || !s.bf[2] || !s.rbn_s || !s.rbn_h) return false;
+  // conv_st_in: its own planes from the model input it reads; conv_st_out: the model input as residual
+  return k == CHAIN_IN ? a.s0.out && a.s0.xin == s.x && s.xmodel : g.xres != nullptr;
 }
 
-hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a) {
-  return chain_append_enc(c->s, c->t, c->enc, c->nblk, kEncChainMax, a);
+// the whole block b of kind PH as c carries it: what the kernel's accessors will read
+template <int PH, typename A>
+static BlockFusedArgs chain_block(const A* c, int b) {
+  return BlockFusedArgs{chain_block_s<PH>(c, b),
+                        TemporalFusedArgs{chain_block_g<PH>(c, b), chain_block_j<PH>(c, b), chain_block_sn<PH>(c, b)},
+                        chain_block_s0<PH>(c, b)};
 }
+BlockFusedArgs enc_chain_block(const EncChainArgs& c, int b) { return chain_block<CHAIN_ENC>(&c, b); }
+BlockFusedArgs model_chain_block(const ModelChainArgs& c, int kind, int b) {
+  return kind == CHAIN_IN    ? chain_block<CHAIN_IN>(&c, 0)
+         : kind == CHAIN_ENC ? chain_block<CHAIN_ENC>(&c, b)
+                             : chain_block<CHAIN_OUT>(&c, 0);
+}
+static bool same_block(const BlockFusedArgs& r, const BlockFusedArgs& a) { return memcmp(&r, &a, sizeof(a)) == 0; }
 
 // the descriptor fields of a block's arguments (for conv_st_out, which has no
 // phase 3 and no P/Q conv, those stay null)
@@ -3245,109 +3314,74 @@ static EncChainDesc enc_chain_desc(const BlockFusedArgs& a) {
   return d;
 }
 
-template <int T, int V>
-hipError_t enc_chain_run(const EncChainArgs& c, hipStream_t s) {
-  using Gm = BlockFusedGeom<T, V, 64, 64, TEPI_ENC>;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)k_enc_chain<T, V>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::LDS);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((k_enc_chain<T, V>), dim3(c.t.g.B), dim3(64 * tf_waves<T, V>()), Gm::LDS, s, c);
-  return hipGetLastError();
+// One more encoder block for a launch that carries the shared geometry (c.s,
+// c.t: the first block's arguments) and a descriptor per block (c.enc[0..n) of
+// cap): k_enc_chain's run and k_model_chain's encoder stack alike.
+template <typename A>
+static hipError_t chain_append_enc(A& c, int& n, int cap, const BlockFusedArgs& a) {
+  if (n >= cap || !chain_kind_ok(CHAIN_ENC, a)) return hipErrorNotSupported;
+  if (n == 0) {
+    c.s = a.s;
+    c.t = a.t;
+  }
+  c.enc[n] = enc_chain_desc(a);
+  if (!same_block(chain_block<CHAIN_ENC>(&c, n), a)) return hipErrorNotSupported;
+  ++n;
+  return hipSuccess;
+}
+
+hipError_t enc_chain_append(EncChainArgs* c, const BlockFusedArgs& a) {
+  return chain_append_enc(*c, c->nblk, kEncChainMax, a);
 }
 
 hipError_t launch_enc_chain(const EncChainArgs& c, hipStream_t s) {
   if (c.nblk < 1 || c.nblk > kEncChainMax) return hipErrorInvalidValue;
-  const int T = c.t.g.T, V = c.t.g.V;
-  if (T == 35 && V == 22) return enc_chain_run<35, 22>(c, s);
-  if (T == 35 && V == 25) return enc_chain_run<35, 25>(c, s);
-  if (T == 40 && V == 23) return enc_chain_run<40, 23>(c, s);
-  return hipErrorNotSupported;
+  return hl_dispatch_block(c.t.g.T, c.t.g.V, [&](auto sh) {
+    constexpr int T = decltype(sh)::T, V = decltype(sh)::V;
+    return launch_per_sample<k_enc_chain<T, V>, T, V, BlockFusedGeom<T, V, 64, 64, TEPI_ENC>::LDS>(c.t.g.B, c, s);
+  });
 }
 
-bool model_chain_supported(int T, int V) {
-  return enc_chain_supported(T, V) && block_fused_adj0_supported(T, V) && block_fused_supported(T, V, 64, 3, TEPI_OUT);
-}
+bool model_chain_complete(const ModelChain& c) { return c.a.nenc >= 1 && c.have == 3; }
 
-bool model_chain_complete(const ModelChainArgs& c) { return c.nenc >= 1 && c.have == 3; }
-
-hipError_t model_chain_append(ModelChainArgs* c, const BlockFusedArgs& a) {
+hipError_t model_chain_append(ModelChain* mc, const BlockFusedArgs& a) {
+  ModelChainArgs& c = mc->a;
   const SpatialHLArgs& s = a.s;
-  const TemporalHLArgs& g = a.t.g;
-  const AdjHLArgs &j = a.t.j, &n = a.t.sn;
-  if (!model_chain_supported(g.T, g.V)) return hipErrorNotSupported;
-  const bool enc = s.Cin == 64 && s.Cout == 64 && g.epi == TEPI_ENC;
-  const bool in = s.Cin == 6 && s.Cout == 64 && g.epi == TEPI_IN, out = s.Cin == 64 && s.Cout == 3 && g.epi == TEPI_OUT;
+  const int k = block_kind(s.Cin, s.Cout, a.t.g.epi), place = k == CHAIN_IN ? 1 : 2;
   // the encoder blocks exactly as a run of k_enc_chain takes them, before the ends
-  if (enc) return c->have ? hipErrorNotSupported : chain_append_enc(c->s, c->t, c->enc, c->nenc, kModelChainMaxEnc, a);
-  if (!(in || out) || c->nenc < 1 || (c->have & (in ? 1 : 2))) return hipErrorNotSupported;
-  // everything outside the compact form is the shared geometry
-  const SpatialHLArgs& sg = c->s;
-  const TemporalHLArgs& gg = c->t.g;
-  const AdjHLArgs &jg = c->t.j, &ng = c->t.sn;
-  if (s.B != sg.B || s.T != sg.T || s.V != sg.V || s.adj != sg.adj || s.pq != sg.pq || g.B != gg.B || g.T != gg.T ||
-      g.V != gg.V || g.adj != gg.adj || !chain_same_adj(j, jg) || j.xin || !s.wimg[2] || !s.wscale[2] || !s.bf[2] ||
-      !s.rbn_s || !s.rbn_h)
-    return hipErrorNotSupported;
-  if (in) {
+  if (k == CHAIN_ENC)
+    return mc->have || !model_chain_supported(a.t.g.T, a.t.g.V) ? hipErrorNotSupported
+                                                        : chain_append_enc(c, c.nenc, kModelChainMaxEnc, a);
+  if (c.nenc < 1 || (mc->have & place) || !chain_kind_ok(k, a)) return hipErrorNotSupported;
+  (k == CHAIN_IN ? c.in : c.out) = ModelEndDesc{enc_chain_desc(a), s.wimg[2], s.wscale[2], s.bf[2], s.rbn_s, s.rbn_h};
+  if (k == CHAIN_IN) {
     const AdjHLArgs& z = a.s0;
-    if (!s.xmodel || g.C != gg.C || g.pq != gg.pq || g.xres || !n.out || n.xin || !chain_same_adj(n, ng) || !z.out ||
-        z.xin != s.x || !chain_same_adj(z, ng))
-      return hipErrorNotSupported;
-  } else {
-    if (s.xmodel || g.C != 3 || g.pq || g.pqimg || g.pqscale || n.out || a.s0.out || !g.xres)
-      return hipErrorNotSupported;
-  }
-  ModelEndDesc& d = in ? c->in : c->out;
-  d = ModelEndDesc{};
-  d.e = enc_chain_desc(a);
-  d.s_wimg2 = s.wimg[2];
-  d.s_wscale2 = s.wscale[2];
-  d.s_bf2 = s.bf[2];
-  d.s_rbn_s = s.rbn_s;
-  d.s_rbn_h = s.rbn_h;
-  if (in) {
-    const AdjHLArgs& z = a.s0;
-    ModelAdj0Desc& q = c->in0;
+    ModelAdj0Desc& q = c.in0;
     q = ModelAdj0Desc{};
     q.xin = z.xin;
-    for (int i = 0; i < 2; ++i) {
-      for (int k = 0; k < 2; ++k) {
-        q.mw[i][k] = z.mw[i][k];
-        q.mb[i][k] = z.mb[i][k];
-      }
-      q.wimg[i] = z.wimg[i];
-      q.wscale[i] = z.wscale[i];
-      q.bias[i] = z.bias[i];
-      q.astat[i] = z.astat[i];
-    }
+    memcpy(q.mw, z.mw, sizeof(q.mw));
+    memcpy(q.mb, z.mb, sizeof(q.mb));
+    memcpy(q.wimg, z.wimg, sizeof(q.wimg));
+    memcpy(q.wscale, z.wscale, sizeof(q.wscale));
+    memcpy(q.bias, z.bias, sizeof(q.bias));
+    memcpy(q.astat, z.astat, sizeof(q.astat));
     q.alpha = z.alpha;
   }
-  c->have |= in ? 1 : 2;
+  if (!same_block(model_chain_block(c, k, 0), a)) return hipErrorNotSupported;
+  mc->have |= place;
   return hipSuccess;
 }
 
-template <int T, int V>
-hipError_t model_chain_run(const ModelChainArgs& c, hipStream_t s) {
-  using Gm = ModelChainGeom<T, V>;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)k_model_chain<T, V>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gm::LDS);
-  if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((k_model_chain<T, V>), dim3(c.t.g.B), dim3(64 * tf_waves<T, V>()), Gm::LDS, s, c);
-  return hipGetLastError();
+hipError_t launch_model_chain(const ModelChain& c, hipStream_t s) {
+  if (!model_chain_complete(c) || c.a.nenc > kModelChainMaxEnc) return hipErrorInvalidValue;
+  return hl_dispatch_block(c.a.t.g.T, c.a.t.g.V, [&](auto sh) {
+    constexpr int T = decltype(sh)::T, V = decltype(sh)::V;
+    return launch_per_sample<k_model_chain<T, V>, T, V, ModelChainGeom<T, V>::LDS>(c.a.t.g.B, c.a, s);
+  });
 }
 
-hipError_t launch_model_chain(const ModelChainArgs& c, hipStream_t s) {
-  if (!model_chain_complete(c) || c.nenc > kModelChainMaxEnc) return hipErrorInvalidValue;
-  const int T = c.t.g.T, V = c.t.g.V;
-  if (T == 35 && V == 22) return model_chain_run<35, 22>(c, s);
-  if (T == 35 && V == 25) return model_chain_run<35, 25>(c, s);
-  if (T == 40 && V == 23) return model_chain_run<40, 23>(c, s);
-  return hipErrorNotSupported;
-}
 
-bool temporal_fused_supported(int T, int V) {
-  return (T == 35 && (V == 22 || V == 25)) || (T == 40 && V == 23) || (T == 75 && V == 22);
-}
+bool temporal_fused_supported(int T, int V) { return hl_shape(T, V); }
 // the schedule's default at full batch: T = 75 runs its u chunks only when
 // asked (DSTD_FWD_FUSED_TEMPORAL) -- measured 8.8% slower per forward than the
 // unfused pair (profiles/r05h_t75_fused_ab.txt)
@@ -3355,11 +3389,7 @@ bool temporal_fused_default(int T, int V) {
   return temporal_fused_supported(T, V) && T != 75;
 }
 bool temporal_fused_phase3(int T, int V) {
-  if (T == 35 && V == 22) return tf_phase3<35, 22>();
-  if (T == 35 && V == 25) return tf_phase3<35, 25>();
-  if (T == 40 && V == 23) return tf_phase3<40, 23>();
-  if (T == 75 && V == 22) return tf_phase3<75, 22>();
-  return false;
+  return hl_shape_is(T, V, [](auto sh) { return tf_phase3<decltype(sh)::T, decltype(sh)::V>(); });
 }
 
 hipError_t launch_temporal_fused(const TemporalHLArgs& g, const AdjHLArgs& j, const AdjHLArgs* sn, hipStream_t s) {
@@ -3368,11 +3398,7 @@ hipError_t launch_temporal_fused(const TemporalHLArgs& g, const AdjHLArgs& j, co
     return hipErrorNotSupported;
   if (sn && !phase3_args_ok(g, *sn)) return hipErrorNotSupported;
   const TemporalFusedArgs a{g, j, sn ? *sn : AdjHLArgs{}};
-  if (g.T == 35 && g.V == 22) return tfused_tv<35, 22>(a, s);
-  if (g.T == 35 && g.V == 25) return tfused_tv<35, 25>(a, s);
-  if (g.T == 40 && g.V == 23) return tfused_tv<40, 23>(a, s);
-  if (g.T == 75 && g.V == 22) return tfused_tv<75, 22>(a, s);
-  return hipErrorNotSupported;
+  return hl_dispatch(g.T, g.V, [&](auto sh) { return tfused_tv<decltype(sh)::T, decltype(sh)::V>(a, s); });
 }
 
 hipError_t launch_temporal_hl(const TemporalHLArgs& a, hipStream_t s) {

@@ -46,6 +46,7 @@ struct FoldArgs {
 struct PQLayout {
   long sn;
   int sch, st, sv;
+  int pad_;  // zero: the tail padding, named so that the struct compares bytewise (dstd_hilo.h, chain launches)
 };
 inline PQLayout pq_layout_vt(int nch, int T, int V) { return PQLayout{(long)nch * T * V, 1, nch, nch * T}; }
 inline PQLayout pq_layout_tv(int nch, int T, int V) { return PQLayout{(long)nch * T * V, 1, nch * V, nch}; }
