@@ -7,6 +7,7 @@
 #include "dstd_train.h"
 
 #include <algorithm>
+#include <initializer_list>
 #include <type_traits>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1753,36 +1754,148 @@ __global__ __launch_bounds__(256) void k_bn_merge(BnFwd a, int rows, int splits,
     ss[((size_t)g * a.cv + ch) * 2 + 1] = a.beta[ch] - mean * sc;
   }
 }
-__global__ __launch_bounds__(256) void k_bn_apply_flat(BnFwd a, int Bg, int C, int TV, int V, long long total,
-                                                       const float* ss) {
-  const float w = a.prelu ? *a.prelu : 0.f;
+
+// ---- the element-wise apply, both directions ---------------------------------
+// The arithmetic of an element is written once per direction (bn_fwd_elem,
+// bn_bwd_elem below); a kernel hands it its channel's coefficients through an
+// accessor indexed by the joint v: LDS arrays in the merged kernels, the
+// separate merge's tables in the flat ones.  A float4 item is loaded
+// (bn_*_load4), then run lane by lane through the element function with the
+// joint rotating and stored (bn_*_lanes4).  Three enumerations turn an item
+// index into (offset, first joint) -- and pick the accessor's group --, each
+// shared by the two directions: bn_flat_items4, bn_plane_items4 (merged VEC),
+// bn_plane_items1 (merged scalar).
+__device__ __forceinline__ float4 ld4_opt(const float* p, size_t at) {
+  return p ? ld4(p + at) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ float4 ld4_u(const float* x, const float* x2, size_t at) {  // u = x (+ x2)
+  float4 u = ld4(x + at);
+  if (x2) {
+    const float4 u2 = ld4(x2 + at);
+    u.x += u2.x, u.y += u2.y, u.z += u2.z, u.w += u2.w;
+  }
+  return u;
+}
+__device__ __forceinline__ void st4(float* p, const float (&v)[4]) {
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// Flat: every float4 of the tensor, grid-stride; f(offset, first joint, c, group)
+template <class F>
+__device__ __forceinline__ void bn_flat_items4(int Bg, int C, int TV, int V, long long total, F f) {
   const int stride = gridDim.x * 256 * 4, tot = (int)total;  // (the launcher keeps total < 2^31)
   for (int i0 = (blockIdx.x * 256 + threadIdx.x) * 4; i0 < tot; i0 += stride) {
     // TV % 4 == 0: the 4 elements share (n, c)
     const int nc = i0 / TV;
     const int e0 = i0 - nc * TV, n = nc / C, c = nc - n * C, g = n / Bg;
-    float4 u = *reinterpret_cast<const float4*>(a.x + i0);
-    if (a.x2) {
-      const float4 u2 = *reinterpret_cast<const float4*>(a.x2 + i0);
-      u.x += u2.x, u.y += u2.y, u.z += u2.z, u.w += u2.w;
-    }
-    const float4 r = a.res ? *reinterpret_cast<const float4*>(a.res + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float uu[4] = {u.x, u.y, u.z, u.w}, rr[4] = {r.x, r.y, r.z, r.w};
-    float zz[4], oo[4];
-    int v = e0 % V;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float* q = ss + ((size_t)g * a.cv + c * V + v) * 2;
-      float z = fmaf(uu[j], q[0], q[1]);
-      if (a.res) z += rr[j];
-      zz[j] = z;
-      oo[j] = a.prelu ? prelu_f(z, w) : z;
-      v = v + 1 == V ? 0 : v + 1;
-    }
-    if (a.prelu) *reinterpret_cast<float4*>(a.zsave + i0) = make_float4(zz[0], zz[1], zz[2], zz[3]);
-    *reinterpret_cast<float4*>(a.out + i0) = make_float4(oo[0], oo[1], oo[2], oo[3]);
+    f((size_t)i0, e0 % V, c, g);
   }
 }
+
+// Merged, VEC: the planes [T][V] of channel c, samples n .. n + ns - 1, as one
+// run of ns T V / 4 float4 items; a thread takes EB of them per batch, all
+// loads of a batch issued before the first use.  load(offset) gives the item,
+// use(item, offset, first joint) consumes it.
+template <class Load, class Use>
+__device__ __forceinline__ void bn_plane_items4(int n, int c, int C, int T, int V, int ns, Load load, Use use) {
+  constexpr int EB = 2;  // float4 items per thread per batch, loads issued first
+  const int tv4 = T * V / 4, tot = ns * tv4;
+  const FastDiv divV(V);
+  for (int i0 = threadIdx.x; i0 < tot; i0 += EB * 256) {
+    decltype(load((size_t)0)) it[EB];
+    size_t at[EB];
+    int vv[EB];
+#pragma unroll
+    for (int j = 0; j < EB; ++j) {
+      const int i = min(i0 + j * 256, tot - 1);  // (clamped: loads without branches)
+      const int k = (i >= tv4) + (i >= 2 * tv4) + (i >= 3 * tv4), e = 4 * (i - k * tv4);  // (ns <= 4)
+      at[j] = ((size_t)(n + k) * C + c) * T * V + e;
+      vv[j] = e - divV(e) * V;
+      it[j] = load(at[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < EB; ++j) {
+      if (i0 + j * 256 >= tot) break;
+      use(it[j], at[j], vv[j]);
+    }
+  }
+}
+
+// Merged, scalar (T V % 4 != 0 or an unaligned tensor): plane by plane, EB
+// elements per thread per batch.  load(offset, inside) gives the element,
+// use(element, offset, joint) consumes it.  (Kept as a loop of its own, not
+// bn_plane_items4 at item width 1: that would be another kernel to measure.)
+template <class Load, class Use>
+__device__ __forceinline__ void bn_plane_items1(int n, int c, int C, int T, int V, int ns, Load load, Use use) {
+  constexpr int EB = 4;  // elements per thread per batch, loads issued first
+  for (int k = 0; k < ns; ++k)
+  for (int e0 = threadIdx.x; e0 < T * V; e0 += EB * 256) {
+    const size_t base = ((size_t)(n + k) * C + c) * T * V;
+    decltype(load((size_t)0, true)) it[EB];
+#pragma unroll
+    for (int j = 0; j < EB; ++j) {
+      const int e = e0 + j * 256;
+      it[j] = load(base + e, e < T * V);
+    }
+#pragma unroll
+    for (int j = 0; j < EB; ++j) {
+      const int e = e0 + j * 256;
+      if (e >= T * V) break;
+      use(it[j], base + e, e % V);
+    }
+  }
+}
+
+// ---- forward: z = scale u + shift (+ res), out = PReLU(z) (or z) -------------
+template <class K>
+__device__ __forceinline__ float bn_fwd_elem(const BnFwd& a, float w, float u, float r, const K& k, int v, float& z) {
+  z = fmaf(u, k.scale(v), k.shift(v));
+  if (a.res) z += r;
+  return a.prelu ? prelu_f(z, w) : z;
+}
+struct BnFwd4 {
+  float4 u, r;
+};
+__device__ __forceinline__ BnFwd4 bn_fwd_load4(const BnFwd& a, size_t at) {
+  BnFwd4 it;
+  it.u = ld4_u(a.x, a.x2, at);
+  it.r = ld4_opt(a.res, at);
+  return it;
+}
+template <class K>
+__device__ __forceinline__ void bn_fwd_lanes4(const BnFwd& a, float w, const BnFwd4& it, size_t at, const K& k, int v,
+                                              int V) {
+  const float uu[4] = {it.u.x, it.u.y, it.u.z, it.u.w}, rr[4] = {it.r.x, it.r.y, it.r.z, it.r.w};
+  float zz[4], oo[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    oo[q] = bn_fwd_elem(a, w, uu[q], rr[q], k, v, zz[q]);
+    v = v + 1 == V ? 0 : v + 1;
+  }
+  if (a.prelu) st4(a.zsave + at, zz);
+  st4(a.out + at, oo);
+}
+
+struct BnFwdFlatCoef {  // channel (c, .) of group g in k_bn_merge's ss[group][C*V][2]
+  const float* q;
+  __device__ float scale(int v) const { return q[2 * v]; }
+  __device__ float shift(int v) const { return q[2 * v + 1]; }
+};
+__global__ __launch_bounds__(256) void k_bn_apply_flat(BnFwd a, int Bg, int C, int TV, int V, long long total,
+                                                       const float* ss) {
+  const float w = a.prelu ? *a.prelu : 0.f;
+  bn_flat_items4(Bg, C, TV, V, total, [&](size_t at, int v0, int c, int g) {
+    const BnFwdFlatCoef k{ss + ((size_t)g * a.cv + c * V) * 2};
+    bn_fwd_lanes4(a, w, bn_fwd_load4(a, at), at, k, v0, V);
+  });
+}
+
+struct BnFwdLdsCoef {  // the workgroup's channel, per joint
+  float scl[kBnMaxV], shl[kBnMaxV];
+  __device__ float scale(int v) const { return scl[v]; }
+  __device__ float shift(int v) const { return shl[v]; }
+};
+static_assert(kBnMaxV <= 256, "threads tid < V fill the per-joint LDS arrays (V <= kBnMaxV: the launchers' guard)");
 
 // workgroup (c, y) covers samples [ns*y, ns*y + ns) (one group: ns divides B/groups)
 // VEC: T V % 4 == 0 and 16-byte aligned tensors -- the ns planes of channel c
@@ -1790,7 +1903,7 @@ __global__ __launch_bounds__(256) void k_bn_apply_flat(BnFwd a, int Bg, int C, i
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_bn_apply_merged(BnFwd a, int B, int C, int T, int V, int splits,
                                                          const float* part, int ns) {
-  __shared__ float scl[kBnMaxV], shl[kBnMaxV];
+  __shared__ BnFwdLdsCoef L;
   // channel c's split partials of the groups this workgroup merges, staged
   // with every load in flight at once (merging straight from memory chains
   // 2 x splits dependent loads per group)
@@ -1824,80 +1937,31 @@ __global__ __launch_bounds__(256) void k_bn_apply_merged(BnFwd a, int B, int C, 
     bn_merge_stats(a, ch, tid, V, Bg * T, splits, pl, n == 0 ? a.groups - 1 : g, mean, rstd, n == 0);
     if (n == 0 && a.groups > 1) bn_merge_stats(a, ch, tid, V, Bg * T, splits, pl, 0, mean, rstd, false);
     const float sc = rstd * a.gamma[ch];
-    scl[tid] = sc;
-    shl[tid] = a.beta[ch] - mean * sc;
+    L.scl[tid] = sc;
+    L.shl[tid] = a.beta[ch] - mean * sc;
   }
   __syncthreads();
   const float w = a.prelu ? *a.prelu : 0.f;
   if constexpr (VEC) {
-    constexpr int EB = 2;  // float4 items per thread per batch, loads issued first
-    const int tv4 = T * V / 4, tot = ns * tv4;
-    const FastDiv divV(V);
-    for (int i0 = tid; i0 < tot; i0 += EB * 256) {
-      float4 u[EB], r[EB];
-      size_t at[EB];
-      int vv[EB];
-#pragma unroll
-      for (int j = 0; j < EB; ++j) {
-        const int i = min(i0 + j * 256, tot - 1);  // (clamped: loads without branches)
-        const int k = (i >= tv4) + (i >= 2 * tv4) + (i >= 3 * tv4), e = 4 * (i - k * tv4);
-        at[j] = ((size_t)(n + k) * C + c) * T * V + e;
-        vv[j] = e - divV(e) * V;
-        u[j] = ld4(a.x + at[j]);
-        if (a.x2) {
-          const float4 u2 = ld4(a.x2 + at[j]);
-          u[j].x += u2.x, u[j].y += u2.y, u[j].z += u2.z, u[j].w += u2.w;
-        }
-        r[j] = a.res ? ld4(a.res + at[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int j = 0; j < EB; ++j) {
-        if (i0 + j * 256 >= tot) break;
-        const float uu[4] = {u[j].x, u[j].y, u[j].z, u[j].w}, rr[4] = {r[j].x, r[j].y, r[j].z, r[j].w};
-        float zz[4], oo[4];
-        int v = vv[j];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float z = fmaf(uu[q], scl[v], shl[v]);
-          if (a.res) z += rr[q];
-          zz[q] = z;
-          oo[q] = a.prelu ? prelu_f(z, w) : z;
-          v = v + 1 == V ? 0 : v + 1;
-        }
-        if (a.prelu) *reinterpret_cast<float4*>(a.zsave + at[j]) = make_float4(zz[0], zz[1], zz[2], zz[3]);
-        *reinterpret_cast<float4*>(a.out + at[j]) = make_float4(oo[0], oo[1], oo[2], oo[3]);
-      }
-    }
+    bn_plane_items4(
+        n, c, C, T, V, ns, [&](size_t at) { return bn_fwd_load4(a, at); },
+        [&](const BnFwd4& it, size_t at, int v0) { bn_fwd_lanes4(a, w, it, at, L, v0, V); });
     return;
   }
-  constexpr int EB = 4;  // elements per thread per batch, loads issued first
-  for (int k = 0; k < ns; ++k)
-  for (int e0 = tid; e0 < T * V; e0 += EB * 256) {
-    const size_t base = ((size_t)(n + k) * C + c) * T * V;
-    float u[EB], r[EB];
-#pragma unroll
-    for (int j = 0; j < EB; ++j) {
-      const int e = e0 + j * 256;
-      const size_t i = base + e;
-      u[j] = e < T * V ? (a.x2 ? a.x[i] + a.x2[i] : a.x[i]) : 0.f;
-      r[j] = (e < T * V && a.res) ? a.res[i] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < EB; ++j) {
-      const int e = e0 + j * 256;
-      if (e >= T * V) break;
-      const size_t i = base + e;
-      const int v = e % V;
-      float z = fmaf(u[j], scl[v], shl[v]);
-      if (a.res) z += r[j];
-      if (a.prelu) {
-        a.zsave[i] = z;
-        a.out[i] = prelu_f(z, w);
-      } else {
-        a.out[i] = z;
-      }
-    }
-  }
+  struct El {
+    float u, r;
+  };
+  bn_plane_items1(
+      n, c, C, T, V, ns,
+      [&](size_t i, bool in) {
+        return El{in ? (a.x2 ? a.x[i] + a.x2[i] : a.x[i]) : 0.f, (in && a.res) ? a.res[i] : 0.f};
+      },
+      [&](const El& it, size_t i, int v) {
+        float z;
+        const float o = bn_fwd_elem(a, w, it.u, it.r, L, v, z);
+        if (a.prelu) a.zsave[i] = z;
+        a.out[i] = o;
+      });
 }
 
 // part: [splits][C*V][2] = (sum dz, sum dz*xhat); wpart: [splits][C] PReLU slope partials
@@ -1949,6 +2013,28 @@ __global__ __launch_bounds__(kRedThreads) void k_bn_bwd_part(BnBwd a, int B, int
   }
 }
 
+// (sum dz, sum dz*xhat) of (group g, channel ch) from part, in split order:
+// the loads first, then the sums (one after the other they chain splits
+// dependent loads); splits <= kBnMaxSplits (bn_splits).  The splits past the
+// last load as +0, which the sums add like the rest: a sum that starts at +0
+// is never -0, so adding +0 leaves its bits alone, and the merged backward
+// kernel does not hold kBnMaxSplits conditions in SGPRs across both loops
+// (with them it sits 1 SGPR over the 8-wave limit).
+__device__ __forceinline__ float2 bn_bwd_split_sums(const float* part, int g, int splits, int CV, int ch) {
+  float2 pv[kBnMaxSplits];
+#pragma unroll
+  for (int sp = 0; sp < kBnMaxSplits; ++sp)
+    pv[sp] = sp < splits ? *reinterpret_cast<const float2*>(part + ((size_t)(g * splits + sp) * CV + ch) * 2)
+                         : make_float2(0.f, 0.f);
+  float sd = 0.f, sdx = 0.f;
+#pragma unroll
+  for (int sp = 0; sp < kBnMaxSplits; ++sp) {
+    sd += pv[sp].x;
+    sdx += pv[sp].y;
+  }
+  return make_float2(sd, sdx);
+}
+
 // SyncBN: this rank's (sum dz, sum dz*xhat) per (group, channel), split order,
 // then the groups' row counts -- the buffer the all-reduce sums
 __global__ __launch_bounds__(256) void k_bn_bwd_local_sums(int cv, int groups, int splits, int rows, const float* part,
@@ -1956,21 +2042,15 @@ __global__ __launch_bounds__(256) void k_bn_bwd_local_sums(int cv, int groups, i
   const int ch = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y;
   if (ch == 0) dst[(size_t)groups * cv * 2 + g] = (float)rows;
   if (ch >= cv) return;
-  float sd = 0.f, sdx = 0.f;
-  for (int sp = 0; sp < splits; ++sp) {
-    const float* p = part + ((size_t)(g * splits + sp) * cv + ch) * 2;
-    sd += p[0];
-    sdx += p[1];
-  }
-  dst[((size_t)g * cv + ch) * 2] = sd;
-  dst[((size_t)g * cv + ch) * 2 + 1] = sdx;
+  const float2 t = bn_bwd_split_sums(part, g, splits, cv, ch);
+  dst[((size_t)g * cv + ch) * 2] = t.x;
+  dst[((size_t)g * cv + ch) * 2 + 1] = t.y;
 }
 
 // bn_sep() backward: the merge as a launch of its own (one thread per
 // channel: the group sums in split order into sx[group][C*V][2] -- SyncBN's
 // all-reduced ones for the input gradient -- dgamma / dbeta, and workgroup 0
-// the PReLU slope), then a flat float4 apply.  Same arithmetic as
-// k_bn_bwd_apply_merged.
+// the PReLU slope), then a flat float4 apply.
 __global__ __launch_bounds__(256) void k_bn_bwd_merge(BnBwd a, int splits, int C, const float* part,
                                                       const float* wpart, float* dprelu, float* sx, int CV) {
   __shared__ float red[kRedThreads / 64];
@@ -1984,57 +2064,83 @@ __global__ __launch_bounds__(256) void k_bn_bwd_merge(BnBwd a, int splits, int C
   if (ch >= CV) return;
   float tb = 0.f, tg = 0.f;
   for (int gg = 0; gg < a.groups; ++gg) {
-    float sd = 0.f, sdx = 0.f;
-    for (int sp = 0; sp < splits; ++sp) {
-      const float2 pv = *reinterpret_cast<const float2*>(part + ((size_t)(gg * splits + sp) * CV + ch) * 2);
-      sd += pv.x;
-      sdx += pv.y;
-    }
-    sx[((size_t)gg * CV + ch) * 2] = a.gsum ? a.gsum[((size_t)gg * CV + ch) * 2] : sd;
-    sx[((size_t)gg * CV + ch) * 2 + 1] = a.gsum ? a.gsum[((size_t)gg * CV + ch) * 2 + 1] : sdx;
-    tb += sd;
-    tg += sdx;
+    const float2 t = bn_bwd_split_sums(part, gg, splits, CV, ch);
+    sx[((size_t)gg * CV + ch) * 2] = a.gsum ? a.gsum[((size_t)gg * CV + ch) * 2] : t.x;
+    sx[((size_t)gg * CV + ch) * 2 + 1] = a.gsum ? a.gsum[((size_t)gg * CV + ch) * 2 + 1] : t.y;
+    tb += t.x;
+    tg += t.y;
   }
   a.dbeta[ch] += tb;
   a.dgamma[ch] += tg;
 }
+
+// ---- backward: dz = PReLU'(z) d, du from dz, xhat and the channel's sums -----
+// k: mean / rstd / gamma and the sums (sum dz, sum dz*xhat) of joint v's channel;
+// inv: 1 / the statistics' row count; ad(): the element of dz_add (called only when there is one)
+template <class AD, class K>
+__device__ __forceinline__ float bn_bwd_elem(const BnBwd& a, float w, float inv, float d, float z, float u, AD ad,
+                                             const K& k, int v, float& dz_out) {
+  // PReLU' (torch convention: the slope for z <= 0)
+  const float dz = (a.prelu && !(z > 0.f)) ? w * d : d;
+  const float mean = k.mean(v), rstd = k.rstd(v);
+  const float xh = (u - mean) * rstd;
+  dz_out = a.dz_add ? dz + ad() : dz;
+  return a.use_running ? k.gamma(v) * rstd * dz : k.gamma(v) * rstd * (dz - k.sd(v) * inv - xh * k.sdx(v) * inv);
+}
+struct BnBwd4 {
+  float4 d, z, u, ad;
+};
+__device__ __forceinline__ BnBwd4 bn_bwd_load4(const BnBwd& a, size_t at) {
+  BnBwd4 it;
+  it.d = ld4(a.dout + at);
+  it.z = a.prelu ? ld4(a.zsave + at) : make_float4(0.f, 0.f, 0.f, 0.f);
+  it.u = ld4_u(a.x, a.x2, at);
+  it.ad = ld4_opt(a.dz_add, at);
+  return it;
+}
+template <class K>
+__device__ __forceinline__ void bn_bwd_lanes4(const BnBwd& a, float w, float inv, const BnBwd4& it, size_t at,
+                                              const K& k, int v, int V) {
+  const float dv[4] = {it.d.x, it.d.y, it.d.z, it.d.w}, zv[4] = {it.z.x, it.z.y, it.z.z, it.z.w};
+  const float uv[4] = {it.u.x, it.u.y, it.u.z, it.u.w}, av[4] = {it.ad.x, it.ad.y, it.ad.z, it.ad.w};
+  float du[4], dzo[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    du[q] = bn_bwd_elem(a, w, inv, dv[q], zv[q], uv[q], [&] { return av[q]; }, k, v, dzo[q]);
+    v = v + 1 == V ? 0 : v + 1;
+  }
+  st4(a.du + at, du);
+  if (a.dz_out) st4(a.dz_out + at, dzo);
+}
+
+struct BnBwdFlatCoef {  // channel (c, .) of group g: the saved statistics and k_bn_bwd_merge's sx[group][C*V][2]
+  const float *mn, *rs, *gm, *sx;
+  __device__ float mean(int v) const { return mn[v]; }
+  __device__ float rstd(int v) const { return rs[v]; }
+  __device__ float gamma(int v) const { return gm[v]; }
+  __device__ float sd(int v) const { return sx[2 * v]; }
+  __device__ float sdx(int v) const { return sx[2 * v + 1]; }
+};
 __global__ __launch_bounds__(256) void k_bn_bwd_apply_flat(BnBwd a, int Bg, int C, int TV, int V, int T,
                                                            long long total, const float* sx) {
   const float w = a.prelu ? *a.prelu : 0.f;
   const int CV = C * V;
-  const int stride = gridDim.x * 256 * 4, tot = (int)total;  // (the launcher keeps total < 2^31)
-  for (int i0 = (blockIdx.x * 256 + threadIdx.x) * 4; i0 < tot; i0 += stride) {
-    const int nc = i0 / TV;
-    const int e0 = i0 - nc * TV, n = nc / C, c = nc - n * C, g = n / Bg;
+  bn_flat_items4(Bg, C, TV, V, total, [&](size_t at, int v0, int c, int g) {
     const float inv = 1.f / (a.gsum ? a.gsum[(size_t)a.groups * CV * 2 + g] : (float)(Bg * T));
-    const float4 d4 = *reinterpret_cast<const float4*>(a.dout + i0);
-    const float4 z4 = a.prelu ? *reinterpret_cast<const float4*>(a.zsave + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 u4 = *reinterpret_cast<const float4*>(a.x + i0);
-    if (a.x2) {
-      const float4 u2 = *reinterpret_cast<const float4*>(a.x2 + i0);
-      u4.x += u2.x, u4.y += u2.y, u4.z += u2.z, u4.w += u2.w;
-    }
-    const float4 ad4 = a.dz_add ? *reinterpret_cast<const float4*>(a.dz_add + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float dv[4] = {d4.x, d4.y, d4.z, d4.w}, zv[4] = {z4.x, z4.y, z4.z, z4.w}, uv[4] = {u4.x, u4.y, u4.z, u4.w};
-    const float av[4] = {ad4.x, ad4.y, ad4.z, ad4.w};
-    float du[4], dzo[4];
-    int v = e0 % V;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int ch = c * V + v;
-      const float d = dv[j];
-      const float dz = (a.prelu && !(zv[j] > 0.f)) ? w * d : d;
-      const float mean = a.mean[g * CV + ch], rstd = a.rstd[g * CV + ch], gm = a.gamma[ch];
-      const float xh = (uv[j] - mean) * rstd;
-      const float sdl = sx[((size_t)g * CV + ch) * 2], sxl = sx[((size_t)g * CV + ch) * 2 + 1];
-      du[j] = a.use_running ? gm * rstd * dz : gm * rstd * (dz - sdl * inv - xh * sxl * inv);
-      dzo[j] = a.dz_add ? dz + av[j] : dz;
-      v = v + 1 == V ? 0 : v + 1;
-    }
-    *reinterpret_cast<float4*>(a.du + i0) = make_float4(du[0], du[1], du[2], du[3]);
-    if (a.dz_out) *reinterpret_cast<float4*>(a.dz_out + i0) = make_float4(dzo[0], dzo[1], dzo[2], dzo[3]);
-  }
+    const int ch0 = c * V;
+    const BnBwdFlatCoef k{a.mean + g * CV + ch0, a.rstd + g * CV + ch0, a.gamma + ch0, sx + ((size_t)g * CV + ch0) * 2};
+    bn_bwd_lanes4(a, w, inv, bn_bwd_load4(a, at), at, k, v0, V);
+  });
 }
+
+struct BnBwdLdsCoef {  // the workgroup's channel, per joint: the group's mean / rstd, gamma, the group's sums
+  float mnl[kBnMaxV], rsl[kBnMaxV], gml[kBnMaxV], sdl[kBnMaxV], sxl[kBnMaxV];
+  __device__ float mean(int v) const { return mnl[v]; }
+  __device__ float rstd(int v) const { return rsl[v]; }
+  __device__ float gamma(int v) const { return gml[v]; }
+  __device__ float sd(int v) const { return sdl[v]; }
+  __device__ float sdx(int v) const { return sxl[v]; }
+};
 
 // Merge + apply of the backward in one launch: workgroup (c, n) sums the
 // split partials of its V channels (split order), the n == 0 one accumulates
@@ -2044,39 +2150,29 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply_merged(BnBwd a, int B, int C, int T, int V, int splits,
                                                              const float* part, const float* wpart, float* dprelu,
                                                              int ns) {
-  __shared__ float sdl[kBnMaxV], sxl[kBnMaxV], red[kRedThreads / 64];
-  __shared__ float mnl[kBnMaxV], rsl[kBnMaxV], gml[kBnMaxV];  // the group's mean / rstd and gamma per v
+  __shared__ BnBwdLdsCoef L;
+  __shared__ float red[kRedThreads / 64];
   const int c = blockIdx.x, n = blockIdx.y * ns, tid = threadIdx.x;
   const int CV = C * V;
   const int Bg = B / a.groups, grp = n / Bg;
   if (tid < V) {
     const int ch = c * V + tid;
-    mnl[tid] = a.mean[grp * CV + ch];
-    rsl[tid] = a.rstd[grp * CV + ch];
-    gml[tid] = a.gamma[ch];
+    L.mnl[tid] = a.mean[grp * CV + ch];
+    L.rsl[tid] = a.rstd[grp * CV + ch];
+    L.gml[tid] = a.gamma[ch];
     // group sums; workgroup (c, 0) adds every group's into dgamma / dbeta
     float tb = 0.f, tg = 0.f;
     for (int gg = 0; gg < a.groups; ++gg) {
       if (n != 0 && gg != grp) continue;
-      float2 pv[kBnMaxSplits];  // loads first, then the split-order sums
-#pragma unroll
-      for (int sp = 0; sp < kBnMaxSplits; ++sp)
-        if (sp < splits) pv[sp] = *reinterpret_cast<const float2*>(part + ((size_t)(gg * splits + sp) * CV + ch) * 2);
-      float sd = 0.f, sdx = 0.f;
-#pragma unroll
-      for (int sp = 0; sp < kBnMaxSplits; ++sp)
-        if (sp < splits) {
-          sd += pv[sp].x;
-          sdx += pv[sp].y;
-        }
+      const float2 t = bn_bwd_split_sums(part, gg, splits, CV, ch);
       if (gg == grp) {
         // SyncBN: the input gradient takes every rank's sums; dgamma / dbeta
         // (below) stay this rank's
-        sdl[tid] = a.gsum ? a.gsum[((size_t)grp * CV + ch) * 2] : sd;
-        sxl[tid] = a.gsum ? a.gsum[((size_t)grp * CV + ch) * 2 + 1] : sdx;
+        L.sdl[tid] = a.gsum ? a.gsum[((size_t)grp * CV + ch) * 2] : t.x;
+        L.sxl[tid] = a.gsum ? a.gsum[((size_t)grp * CV + ch) * 2 + 1] : t.y;
       }
-      tb += sd;
-      tg += sdx;
+      tb += t.x;
+      tg += t.y;
     }
     if (n == 0) {
       a.dbeta[ch] += tb;
@@ -2092,80 +2188,26 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply_merged(BnBwd a, int B, int
   __syncthreads();
   const float w = a.prelu ? *a.prelu : 0.f;
   const float inv = 1.f / (a.gsum ? a.gsum[(size_t)a.groups * CV * 2 + grp] : (float)(Bg * T));
-  if constexpr (VEC) {  // (k_bn_apply_merged VEC: float4 items over the ns planes)
-    constexpr int EB = 2;
-    const int tv4 = T * V / 4, tot = ns * tv4;
-    const FastDiv divV(V);
-    for (int i0 = tid; i0 < tot; i0 += EB * 256) {
-      float4 d4[EB], z4[EB], u4[EB], a4[EB];
-      size_t at[EB];
-      int vv[EB];
-#pragma unroll
-      for (int j = 0; j < EB; ++j) {
-        const int i = min(i0 + j * 256, tot - 1);
-        const int k = (i >= tv4) + (i >= 2 * tv4) + (i >= 3 * tv4), e = 4 * (i - k * tv4);
-        at[j] = ((size_t)(n + k) * C + c) * T * V + e;
-        vv[j] = e - divV(e) * V;
-        d4[j] = ld4(a.dout + at[j]);
-        z4[j] = a.prelu ? ld4(a.zsave + at[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        u4[j] = ld4(a.x + at[j]);
-        if (a.x2) {
-          const float4 u2 = ld4(a.x2 + at[j]);
-          u4[j].x += u2.x, u4[j].y += u2.y, u4[j].z += u2.z, u4[j].w += u2.w;
-        }
-        a4[j] = a.dz_add ? ld4(a.dz_add + at[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int j = 0; j < EB; ++j) {
-        if (i0 + j * 256 >= tot) break;
-        const float dv[4] = {d4[j].x, d4[j].y, d4[j].z, d4[j].w}, zv[4] = {z4[j].x, z4[j].y, z4[j].z, z4[j].w};
-        const float uv[4] = {u4[j].x, u4[j].y, u4[j].z, u4[j].w}, av[4] = {a4[j].x, a4[j].y, a4[j].z, a4[j].w};
-        float du[4], dzo[4];
-        int v = vv[j];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float d = dv[q];
-          const float dz = (a.prelu && !(zv[q] > 0.f)) ? w * d : d;
-          const float mean = mnl[v], rstd = rsl[v];
-          const float xh = (uv[q] - mean) * rstd;
-          du[q] = a.use_running ? gml[v] * rstd * dz : gml[v] * rstd * (dz - sdl[v] * inv - xh * sxl[v] * inv);
-          dzo[q] = a.dz_add ? dz + av[q] : dz;
-          v = v + 1 == V ? 0 : v + 1;
-        }
-        *reinterpret_cast<float4*>(a.du + at[j]) = make_float4(du[0], du[1], du[2], du[3]);
-        if (a.dz_out) *reinterpret_cast<float4*>(a.dz_out + at[j]) = make_float4(dzo[0], dzo[1], dzo[2], dzo[3]);
-      }
-    }
+  if constexpr (VEC) {
+    bn_plane_items4(
+        n, c, C, T, V, ns, [&](size_t at) { return bn_bwd_load4(a, at); },
+        [&](const BnBwd4& it, size_t at, int v0) { bn_bwd_lanes4(a, w, inv, it, at, L, v0, V); });
     return;
   }
-  constexpr int EB = 4;  // elements per thread per batch, loads issued first
-  for (int k = 0; k < ns; ++k)
-  for (int e0 = tid; e0 < T * V; e0 += EB * 256) {
-    const size_t base = ((size_t)(n + k) * C + c) * T * V;
-    float dv[EB], zv[EB], uv[EB];
-#pragma unroll
-    for (int j = 0; j < EB; ++j) {
-      const int e = e0 + j * 256;
-      const size_t i = base + e;
-      const bool in = e < T * V;
-      dv[j] = in ? a.dout[i] : 0.f;
-      zv[j] = (in && a.prelu) ? a.zsave[i] : 0.f;
-      uv[j] = in ? (a.x2 ? a.x[i] + a.x2[i] : a.x[i]) : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < EB; ++j) {
-      const int e = e0 + j * 256;
-      if (e >= T * V) break;
-      const size_t i = base + e;
-      const int v = e % V;
-      const float d = dv[j];
-      const float dz = (a.prelu && !(zv[j] > 0.f)) ? w * d : d;
-      const float mean = mnl[v], rstd = rsl[v];
-      const float xh = (uv[j] - mean) * rstd;
-      a.du[i] = a.use_running ? gml[v] * rstd * dz : gml[v] * rstd * (dz - sdl[v] * inv - xh * sxl[v] * inv);
-      if (a.dz_out) a.dz_out[i] = a.dz_add ? dz + a.dz_add[i] : dz;
-    }
-  }
+  struct El {
+    float d, z, u;
+  };
+  bn_plane_items1(
+      n, c, C, T, V, ns,
+      [&](size_t i, bool in) {
+        return El{in ? a.dout[i] : 0.f, (in && a.prelu) ? a.zsave[i] : 0.f,
+                  in ? (a.x2 ? a.x[i] + a.x2[i] : a.x[i]) : 0.f};
+      },
+      [&](const El& it, size_t i, int v) {
+        float dzo;  // (dz_add is read here, after the batch's loads, and only for a dz_out)
+        a.du[i] = bn_bwd_elem(a, w, inv, it.d, it.z, it.u, [&] { return a.dz_out ? a.dz_add[i] : 0.f; }, L, v, dzo);
+        if (a.dz_out) a.dz_out[i] = dzo;
+      });
 }
 
 // ---------------------------------------------------------------------------
@@ -2861,11 +2903,39 @@ size_t bn_scratch_floats(int B, int C, int T, int V) {  // sized for up to 2 gro
   return 2 * ((size_t)bn_splits(B, T) * C * V * 2 + (size_t)bn_splits(B, T) * C) + (size_t)2 * C * V + (size_t)4 * C * V;
 }
 
+// Which apply a BatchNorm takes, both directions: after a separate merge the
+// flat float4 kernel (ns 0: it has no workgroup planes), else the merged
+// kernel over ns samples per workgroup, by float4 items (T V % 4 == 0, every
+// tensor 16-byte aligned, ns <= 4: bn_plane_items4's three comparisons) or by
+// elements.  The flat kernels index in int: total < 2^31.
+enum { kBnFlat = 0, kBnMergedVec = 1, kBnMergedScalar = 2 };
+struct BnPath {
+  int path, ns, splits;
+  int code() const { return path | ns << 4 | splits << 8; }  // dstd_debug_bn_last
+};
+static_assert(kBnMaxSplits < 256, "BnPath::code(): splits in bits 8-15, ns <= 4 in bits 4-7");
+static BnPath bn_path(int B, int C, int T, int V, int groups, bool aligned) {
+  const long long total = (long long)B * C * T * V;
+  const bool vec = (T * V) % 4 == 0 && aligned;
+  const int splits = bn_splits(B / groups, T);
+  if (bn_sep(total) && vec && total < (1LL << 31)) return {kBnFlat, 0, splits};
+  const int ns = bn_apply_samples(B / groups, B, C);
+  return {vec && ns <= 4 ? kBnMergedVec : kBnMergedScalar, ns, splits};
+}
+static bool bn_aligned16(std::initializer_list<const void*> ps) {  // (null: absent, aligned)
+  uintptr_t w = 0;
+  for (const void* p : ps) w |= (uintptr_t)p;
+  return w % 16 == 0;
+}
+// the last BatchNorm launch's BnPath::code(), either direction (dstd_debug_bn_last)
+static std::atomic<int> g_bn_last{-1};
+
 hipError_t bn_train_fwd(const BnFwd& a, int B, int C, int T, int V, float* scratch, hipStream_t s) {
   if (V > kBnMaxV) return hipErrorInvalidValue;
   if (a.use_running && (!a.running_mean || !a.running_var)) return hipErrorInvalidValue;
   if (a.groups < 1 || a.groups > 2 || B % a.groups) return hipErrorInvalidValue;
-  const int splits = bn_splits(B / a.groups, T);
+  const BnPath p = bn_path(B, C, T, V, a.groups, bn_aligned16({a.x, a.x2, a.res, a.out, a.zsave}));
+  const int splits = p.splits;
   BnFwd b = a;
   b.cv = C * V;
   if (!a.use_running)
@@ -2881,9 +2951,9 @@ hipError_t bn_train_fwd(const BnFwd& a, int B, int C, int T, int V, float* scrat
     b.gath = y.buf;
     b.world = y.world;
   }
-  const long long total = (long long)B * C * T * V;
-  const bool al = ((uintptr_t)a.x | (uintptr_t)a.x2 | (uintptr_t)a.res | (uintptr_t)a.out | (uintptr_t)a.zsave) % 16 == 0;
-  if (bn_sep(total) && (T * V) % 4 == 0 && al && total < (1LL << 31)) {
+  g_bn_last.store(p.code(), std::memory_order_relaxed);
+  if (p.path == kBnFlat) {
+    const long long total = (long long)B * C * T * V;
     float* ss = scratch + (size_t)a.groups * splits * b.cv * 2;
     k_bn_merge<<<cdiv(b.cv, 256), 256, 0, s>>>(b, (B / a.groups) * T, splits, scratch, ss, C, V);
     const hipError_t e = hipGetLastError();
@@ -2893,18 +2963,18 @@ hipError_t bn_train_fwd(const BnFwd& a, int B, int C, int T, int V, float* scrat
     k_bn_apply_flat<<<grid, 256, 0, s>>>(b, B / a.groups, C, T * V, V, total, ss);
     return hipGetLastError();
   }
-  const int ns = bn_apply_samples(B / a.groups, B, C);
-  if ((T * V) % 4 == 0 && al && ns <= 4)
-    k_bn_apply_merged<true><<<dim3(C, B / ns), 256, 0, s>>>(b, B, C, T, V, splits, scratch, ns);
+  if (p.path == kBnMergedVec)
+    k_bn_apply_merged<true><<<dim3(C, B / p.ns), 256, 0, s>>>(b, B, C, T, V, splits, scratch, p.ns);
   else
-    k_bn_apply_merged<false><<<dim3(C, B / ns), 256, 0, s>>>(b, B, C, T, V, splits, scratch, ns);
+    k_bn_apply_merged<false><<<dim3(C, B / p.ns), 256, 0, s>>>(b, B, C, T, V, splits, scratch, p.ns);
   return hipGetLastError();
 }
 
 hipError_t bn_train_bwd(const BnBwd& a, int B, int C, int T, int V, float* scratch, float* dprelu, hipStream_t s) {
   if (V > kBnMaxV) return hipErrorInvalidValue;
   if (a.groups < 1 || a.groups > 2 || B % a.groups) return hipErrorInvalidValue;
-  const int splits = bn_splits(B / a.groups, T);
+  const BnPath p = bn_path(B, C, T, V, a.groups, bn_aligned16({a.x, a.x2, a.zsave, a.dout, a.du, a.dz_out, a.dz_add}));
+  const int splits = p.splits;
   float* part = scratch;
   float* wpart = part + (size_t)a.groups * splits * C * V * 2;
   k_bn_bwd_part<<<dim3(C, splits * a.groups), kRedThreads, 0, s>>>(a, B, C, T, V, splits, part, wpart);
@@ -2920,26 +2990,22 @@ hipError_t bn_train_bwd(const BnBwd& a, int B, int C, int T, int V, float* scrat
       return collective_failed();
     b.gsum = y.buf;
   }
-  const bool al = ((uintptr_t)a.x | (uintptr_t)a.x2 | (uintptr_t)a.zsave | (uintptr_t)a.dout | (uintptr_t)a.du |
-                   (uintptr_t)a.dz_out | (uintptr_t)a.dz_add) % 16 == 0;
-  {
+  g_bn_last.store(p.code(), std::memory_order_relaxed);
+  if (p.path == kBnFlat) {
     const long long total = (long long)B * C * T * V;
-    if (bn_sep(total) && (T * V) % 4 == 0 && al && total < (1LL << 31)) {
-      const int cv = C * V;
-      float* sx = wpart + (size_t)splits * a.groups * C;
-      k_bn_bwd_merge<<<cdiv(cv, 256), 256, 0, s>>>(b, splits, C, part, wpart, dprelu, sx, cv);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-      const int grid = (int)std::min<long long>(cdiv(total / 4, 256), 8192);
-      k_bn_bwd_apply_flat<<<grid, 256, 0, s>>>(b, B / a.groups, C, T * V, V, T, total, sx);
-      return hipGetLastError();
-    }
+    const int cv = C * V;
+    float* sx = wpart + (size_t)splits * a.groups * C;
+    k_bn_bwd_merge<<<cdiv(cv, 256), 256, 0, s>>>(b, splits, C, part, wpart, dprelu, sx, cv);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int grid = (int)std::min<long long>(cdiv(total / 4, 256), 8192);
+    k_bn_bwd_apply_flat<<<grid, 256, 0, s>>>(b, B / a.groups, C, T * V, V, T, total, sx);
+    return hipGetLastError();
   }
-  const int ns = bn_apply_samples(B / a.groups, B, C);
-  if ((T * V) % 4 == 0 && al && ns <= 4)
-    k_bn_bwd_apply_merged<true><<<dim3(C, B / ns), 256, 0, s>>>(b, B, C, T, V, splits, part, wpart, dprelu, ns);
+  if (p.path == kBnMergedVec)
+    k_bn_bwd_apply_merged<true><<<dim3(C, B / p.ns), 256, 0, s>>>(b, B, C, T, V, splits, part, wpart, dprelu, p.ns);
   else
-    k_bn_bwd_apply_merged<false><<<dim3(C, B / ns), 256, 0, s>>>(b, B, C, T, V, splits, part, wpart, dprelu, ns);
+    k_bn_bwd_apply_merged<false><<<dim3(C, B / p.ns), 256, 0, s>>>(b, B, C, T, V, splits, part, wpart, dprelu, p.ns);
   return hipGetLastError();
 }
 
@@ -2994,3 +3060,5 @@ hipError_t frame_mpjpe(const float* all_seqs, const float* outputs, int B, int T
 
 }  // namespace train
 }  // namespace dstd
+
+extern "C" int dstd_debug_bn_last(void) { return dstd::train::g_bn_last.load(std::memory_order_relaxed); }

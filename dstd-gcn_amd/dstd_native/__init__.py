@@ -337,7 +337,7 @@ TRAIN_EXPORTS = ("dstd_dstdgc_train_saved_bytes", "dstd_dstdgc_train_workspace_b
                  "dstd_model_train_bwd_ex", "dstd_dstdgc_train_saved_bytes_r",
                  "dstd_dstdgc_train_workspace_bytes_r", "dstd_dstdgc_train_fwd_r", "dstd_dstdgc_train_bwd_r",
                  "dstd_bn_sync_buffer_floats", "dstd_model_train_fwd_sync", "dstd_model_train_bwd_sync",
-                 "dstd_debug_aggb_last")
+                 "dstd_debug_aggb_last", "dstd_debug_bn_last")
 AUX_EXPORTS = ("dstd_ctg_workspace_bytes", "dstd_ctg_fwd", "dstd_ctg_bwd", "dstd_conv2d_workspace_bytes",
                "dstd_conv2d_fwd", "dstd_conv2d_bwd")
 LOSS_EXPORTS = ("dstd_losses_workspace_bytes", "dstd_losses_fwd", "dstd_losses_bwd")

@@ -229,6 +229,13 @@ int dstd_frame_mpjpe(const float* all_seqs, const float* outputs, int B, int T, 
  * a-chunk kernel); -1 before the first.  Host-side record for tests. */
 int dstd_debug_aggb_last(void);
 
+/* Diagnostics: which apply the last train-mode BatchNorm launch of this
+ * process took, forward or backward -- bits 0-3 the path (0: flat apply after
+ * a separate merge, 1: merged, float4 items, 2: merged, scalar), bits 4-7 the
+ * samples per workgroup ns (0 on the flat path), bits 8-15 the row splits of
+ * the statistics; -1 before the first.  Host-side record for tests. */
+int dstd_debug_bn_last(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,37 @@ _BLOCK_CH = ((64, 64, "h36m", 22), (6, 64, "cmu", 25), (64, 3, "3dpw", 23))
 BLOCK_EVAL_CASES = [BlockCase(ci, co, lay, T, V, 2) for T in T_BLOCK for ci, co, lay, V in _BLOCK_CH]
 BLOCK_TRAIN_CASES = [BlockCase(ci, co, lay, T, V, B) for T in T_BLOCK for ci, co, lay, V in _BLOCK_CH for B in (1, 4)]
 
+# ---- train-mode BatchNorm apply paths (bn_path, csrc/dstd_train.hip) -----------
+# The smallest blocks whose two BatchNorms (C = 64) put more than one sample in
+# an apply workgroup (ns > 1: C * B / ns >= 1024), by float4 items (T*V % 4 == 0)
+# and by elements; the expected dstd_debug_bn_last() fields ride along.
+BN_FLAT, BN_MERGED_VEC, BN_MERGED_SCALAR = 0, 1, 2
+BN_APPLY_CASES = [
+    BlockCase(64, 64, "h36m", 4, 22, 32),  # 44 items: one clamped batch, k in {0, 1}
+    BlockCase(64, 64, "h36m", 4, 22, 64),  # 88 items, all four k
+    BlockCase(64, 64, "h36m", 26, 22, 64),  # 572 items: a second batch whose second item is past the end
+    BlockCase(6, 64, "cmu", 3, 25, 32),  # T*V = 75 odd, with the residual BatchNorm
+    BlockCase(6, 64, "cmu", 3, 25, 64),  # the same at ns 4
+]
+BN_APPLY_EXPECT = dict(zip(BN_APPLY_CASES, (  # (path, ns, splits)
+    (BN_MERGED_VEC, 2, 2), (BN_MERGED_VEC, 4, 4), (BN_MERGED_VEC, 4, 16),
+    (BN_MERGED_SCALAR, 2, 2), (BN_MERGED_SCALAR, 4, 3))))
+
+
+def bn_path(B, C, T, V, groups=1, aligned=True):
+    """(path, ns, splits) of a train-mode BatchNorm: the arithmetic of bn_path,
+    bn_sep, bn_apply_samples and bn_splits (csrc/dstd_train.hip)."""
+    total, vec, Bg = B * C * T * V, (T * V) % 4 == 0 and aligned, B // groups
+    splits = max(1, min(16, cdiv(Bg * T, 64)))
+    if total >= 1 << 24 and vec and total < 1 << 31:
+        return BN_FLAT, 0, splits
+    ns = next((n for n in (4, 2) if Bg % n == 0 and C * (B // n) >= 1024), 1)
+    return (BN_MERGED_VEC if vec and ns <= 4 else BN_MERGED_SCALAR), ns, splits
+
+
+def bn_code(path, ns, splits):
+    return path | ns << 4 | splits << 8
+
 
 # Cases whose default draw is ill-conditioned in fp32 (tests/test_envelope_host.py
 # measures it): another seed (salt) or input scale, never another shape.
@@ -125,6 +156,8 @@ BLOCK_TRAIN_CASES = [BlockCase(ci, co, lay, T, V, B) for T in T_BLOCK for ci, co
 # fp32-oracle worst tensor of each block case below, the larger of 1 and 8
 # CPU threads, in TUNE order: 5e-6, 2.8e-5, 2.6e-5, 1.5e-5, 1.4e-6, 7.4e-6,
 # 1.9e-5, 9.5e-6, 1.4e-5, 1.7e-5 (half bar 1e-4; every other case <= 4e-5).
+# The two CMU cases of BN_APPLY_CASES: 4.3e-5 and 5.1e-5 at salt 0, 2.6e-5 and
+# 3.9e-5 at salt 3 (the h36m ones 2.0e-6, 4.1e-6, 3.5e-6 as drawn).
 TUNE = {
     OpCase("temporal", 64, 64, 2, 1, 2, 2): dict(salt=0, x_scale=0.5),
     BlockCase(64, 64, "h36m", 2, 22, 1): dict(salt=22, x_scale=0.01),
@@ -137,6 +170,8 @@ TUNE = {
     BlockCase(64, 3, "3dpw", 64, 23, 1): dict(salt=1),
     BlockCase(6, 64, "cmu", 65, 25, 4): dict(salt=2),
     BlockCase(6, 64, "cmu", 113, 25, 4): dict(salt=16),
+    BlockCase(6, 64, "cmu", 3, 25, 32): dict(salt=3),
+    BlockCase(6, 64, "cmu", 3, 25, 64): dict(salt=3),
 }
 
 

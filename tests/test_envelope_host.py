@@ -29,7 +29,7 @@ def test_block_eval_case_is_well_conditioned(c):
     assert err <= E.BLOCK_EVAL_BAR / 2
 
 
-@pytest.mark.parametrize("c", E.BLOCK_TRAIN_CASES, ids=E.case_id)
+@pytest.mark.parametrize("c", E.BLOCK_TRAIN_CASES + E.BN_APPLY_CASES, ids=E.case_id)
 def test_block_train_case_is_well_conditioned(c):
     built = E.build_block_train(c)
     r32, r64 = E.block_train_reference(c, torch.float32, built), E.block_train_reference(c, torch.float64, built)
@@ -40,6 +40,20 @@ def test_block_train_case_is_well_conditioned(c):
     # the batch statistics the running-statistics check (bar 1e-5) is built from
     for (m32, v32), (m64, v64) in zip(r32["stats"], r64["stats"]):
         assert E.rel(m32, m64) <= 5e-6 and E.rel(v32, v64) <= 5e-6
+
+
+def test_bn_apply_cases_take_their_paths():
+    """The launch choice of both BatchNorms (C = 64) of each BN_APPLY_CASES
+    block, by arithmetic, is the one the GPU test expects the library to
+    report; no case reaches the flat path's 2^24 elements."""
+    assert len(set(E.BN_APPLY_CASES)) == 5 and not set(E.BN_APPLY_CASES) & set(E.BLOCK_TRAIN_CASES)
+    for c in E.BN_APPLY_CASES:
+        assert c.cout == 64 and E.bn_path(c.B, c.cout, c.T, c.V) == E.BN_APPLY_EXPECT[c], c
+    assert {E.BN_APPLY_EXPECT[c][:2] for c in E.BN_APPLY_CASES} == {(E.BN_MERGED_VEC, 2), (E.BN_MERGED_VEC, 4),
+                                                                    (E.BN_MERGED_SCALAR, 2), (E.BN_MERGED_SCALAR, 4)}
+    # the paired B=256 3DPW model step of tests/test_gpu_train.py (two groups of 256) is what runs the flat path
+    assert E.bn_path(512, 64, 40, 23, groups=2) == (E.BN_FLAT, 0, 16) and E.bn_path(256, 64, 40, 23)[0] != E.BN_FLAT
+    assert E.bn_path(4, 64, 35, 22) == (E.BN_MERGED_SCALAR, 1, 3) and E.bn_path(8, 64, 40, 23) == (E.BN_MERGED_VEC, 1, 5)
 
 
 def test_builders_are_deterministic():

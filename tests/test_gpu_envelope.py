@@ -154,7 +154,15 @@ def test_block_eval_forward(c):
     assert err <= E.BLOCK_EVAL_BAR
 
 
-@pytest.mark.parametrize("c", E.BLOCK_TRAIN_CASES, ids=E.case_id)
+def _assert_bn_last(c, when):
+    """The last BatchNorm launch took the apply path the case is there for
+    (another value: probably an unaligned tensor -- report it, keep the shape)."""
+    torch.cuda.synchronize()
+    got, want = native.lib().dstd_debug_bn_last(), E.BN_APPLY_EXPECT[c]
+    assert got == E.bn_code(*want), (when, "path, ns, splits", (got & 15, got >> 4 & 15, got >> 8), "expected", want)
+
+
+@pytest.mark.parametrize("c", E.BLOCK_TRAIN_CASES + E.BN_APPLY_CASES, ids=E.case_id)
 def test_block_train_forward_backward(c):
     blk, x, w = E.build_block_train(c)
     assert blk.A_s.data_ptr() == blk.R_s.data_ptr()
@@ -164,7 +172,11 @@ def test_block_train_forward_backward(c):
     _realias(blk)
     xg = x.to(DEV).requires_grad_(True)
     y = blk(xg)
+    if c in E.BN_APPLY_EXPECT:
+        _assert_bn_last(c, "forward")
     (y * w.to(DEV)).sum().backward()
+    if c in E.BN_APPLY_EXPECT:
+        _assert_bn_last(c, "backward")
     grads = {}
     for name, p in blk.named_parameters():
         if name in ("A_s", "A_t"):
