@@ -1,4 +1,4 @@
-"""ctypes binding of the MI355X C ABI (include/dstd_gcn.h).
+"""ctypes binding of the MI355X C ABI (include/*.h; declared in abi.py).
 
 The shared library ``libdstd_gcn.so`` is built in-tree (``make -C dstd-gcn_amd``
 or ``__graft_entry__.build()``).  There is no fallback: if the library is
@@ -9,131 +9,11 @@ import os
 
 import torch
 
+from .abi import *  # noqa: F401,F403 -- the constants, structs and export lists are this package's names
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DSTD_LIB overrides the library (A/B experiments with variant builds)
 LIB_PATH = os.environ.get("DSTD_LIB") or os.path.join(os.path.dirname(_HERE), "libdstd_gcn.so")
-
-MODE_SPATIAL = 0
-MODE_TEMPORAL = 1
-MAX_LAYERS = 16
-
-_fp = ctypes.POINTER(ctypes.c_float)
-
-
-class GCWeights(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("wf", "bf", "wm1", "bm1", "wm2", "bm2", "wrm", "brm")]
-
-
-class BN(ctypes.Structure):
-    _fields_ = [("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("running_mean", ctypes.c_void_p),
-                ("running_var", ctypes.c_void_p), ("eps", ctypes.c_float)]
-
-
-class BlockParams(ctypes.Structure):
-    _fields_ = [("cin", ctypes.c_int), ("cout", ctypes.c_int),
-                ("A_s", ctypes.c_void_p), ("W_s", ctypes.c_void_p), ("R_s", ctypes.c_void_p),
-                ("A_t", ctypes.c_void_p), ("R_t", ctypes.c_void_p),
-                ("alpha_sm", ctypes.c_void_p), ("alpha_tm", ctypes.c_void_p),
-                ("conv_s", GCWeights * 2), ("conv_t", GCWeights), ("bn", BN), ("prelu", ctypes.c_void_p),
-                ("res_w", ctypes.c_void_p), ("res_b", ctypes.c_void_p), ("res_bn", BN)]
-
-
-class ModelParams(ctypes.Structure):
-    _fields_ = [("T", ctypes.c_int), ("V", ctypes.c_int), ("num_layers", ctypes.c_int),
-                ("num_feature", ctypes.c_int), ("in_channels", ctypes.c_int),
-                ("st_in", BlockParams), ("bn_in", BN), ("prelu", ctypes.c_void_p),
-                ("enc", BlockParams * MAX_LAYERS), ("enc_bn", BN * MAX_LAYERS),
-                ("enc_prelu", ctypes.c_void_p * MAX_LAYERS), ("st_out", BlockParams)]
-
-
-class Profile(ctypes.Structure):
-    _fields_ = [("kind_mask", ctypes.c_uint), ("capacity", ctypes.c_int), ("count", ctypes.c_int),
-                ("events", ctypes.POINTER(ctypes.c_void_p)), ("kinds", ctypes.POINTER(ctypes.c_int)),
-                ("block", ctypes.POINTER(ctypes.c_int)), ("only_block", ctypes.c_int)]
-
-
-class Launch(ctypes.Structure):
-    """include/dstd_gcn.h dstd_launch: one entry of a forward's launch schedule."""
-    _fields_ = [("kind", ctypes.c_int), ("first_block", ctypes.c_int), ("num_blocks", ctypes.c_int)]
-
-
-class BlockTaps(ctypes.Structure):
-    """include/dstd_gcn_taps.h dstd_block_taps: where one DSTDGCB's taps go
-    (device pointers to dense fp32; None: not wanted, not written)."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("adj_s", "adj_t", "x", "h")]
-
-
-TAP_NAMES = ("adj_s", "adj_t", "x", "h")
-
-
-class GCGrads(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("wf", "bf", "wm1", "bm1", "wm2", "bm2", "wrm", "brm")]
-
-
-class BNGrads(ctypes.Structure):
-    _fields_ = [("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p)]
-
-
-class BlockGrads(ctypes.Structure):
-    _fields_ = [("W_s", ctypes.c_void_p), ("R_s", ctypes.c_void_p), ("R_t", ctypes.c_void_p),
-                ("alpha_sm", ctypes.c_void_p), ("alpha_tm", ctypes.c_void_p),
-                ("conv_s", GCGrads * 2), ("conv_t", GCGrads), ("bn", BNGrads), ("prelu", ctypes.c_void_p),
-                ("res_w", ctypes.c_void_p), ("res_b", ctypes.c_void_p), ("res_bn", BNGrads)]
-
-
-class ModelGrads(ctypes.Structure):
-    _fields_ = [("st_in", BlockGrads), ("bn_in", BNGrads), ("prelu", ctypes.c_void_p),
-                ("enc", BlockGrads * MAX_LAYERS), ("enc_bn", BNGrads * MAX_LAYERS),
-                ("enc_prelu", ctypes.c_void_p * MAX_LAYERS), ("st_out", BlockGrads)]
-
-
-# include/dstd_gcn_train.h dstd_bn_sync: cross-rank BatchNorm (dstd_dist.BnSync)
-COLL_ALLGATHER, COLL_ALLREDUCE_SUM = 0, 1
-COLLECTIVE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
-                                 ctypes.c_void_p)
-
-
-class BnSyncStruct(ctypes.Structure):
-    _fields_ = [("world", ctypes.c_int), ("rank", ctypes.c_int), ("fn", COLLECTIVE_FN), ("ctx", ctypes.c_void_p),
-                ("buf", ctypes.c_void_p), ("buf_floats", ctypes.c_longlong)]
-
-
-class LossProblem(ctypes.Structure):
-    """include/dstd_gcn_loss.h dstd_loss_problem: pred [B][T][V][3] against targ
-    [B][targ_T][V][3], pred frame s <-> targ frame targ_t0 + targ_step * s."""
-    _fields_ = [("pred", ctypes.c_void_p), ("targ", ctypes.c_void_p), ("B", ctypes.c_int), ("T", ctypes.c_int),
-                ("V", ctypes.c_int), ("targ_T", ctypes.c_int), ("targ_t0", ctypes.c_int), ("targ_step", ctypes.c_int)]
-
-
-class SeqStore(ctypes.Structure):
-    """include/dstd_gcn_data.h dstd_seq_store: frames [F][D] resident on the
-    device, windows as start rows, and the tables a batch is gathered through."""
-    _fields_ = [("frames", ctypes.c_void_p), ("used", ctypes.c_void_p), ("starts", ctypes.c_void_p),
-                ("F", ctypes.c_longlong), ("N", ctypes.c_longlong), ("T", ctypes.c_int), ("D", ctypes.c_int),
-                ("Du", ctypes.c_int), ("dim_used", ctypes.c_void_p), ("frame_in", ctypes.c_void_p),
-                ("frame_inv", ctypes.c_void_p), ("mirror_src", ctypes.c_void_p)]
-
-
-# include/dstd_gcn_loss.h DSTD_LOSS_*: term bits, slot k of a values / coef row is bit 1 << k
-LOSS_JL2, LOSS_TL2, LOSS_CL1, LOSS_CL2 = 1, 2, 4, 8
-LOSS_NTERMS = 4
-
-TRAIN_RUNNING_STATS = 1  # include/dstd_gcn_train.h DSTD_TRAIN_RUNNING_STATS
-TRAIN_PAIRED = 2  # DSTD_TRAIN_PAIRED: two BatchNorm batches of B/2 (a forward pair)
-TRAIN_SEED_DEVICE = 4  # DSTD_TRAIN_SEED_DEVICE: the dropout seed is read from device memory
-TRAIN_ONE_STREAM = 8  # DSTD_TRAIN_ONE_STREAM: no weight-gradient stream in the model backward
-FWD_REUSE_CONSTANTS = 1  # include/dstd_gcn.h DSTD_FWD_REUSE_CONSTANTS
-FWD_EXACT_FP32 = 2  # include/dstd_gcn.h DSTD_FWD_EXACT_FP32
-FWD_SEPARATE_ADJ = 4  # include/dstd_gcn.h DSTD_FWD_SEPARATE_ADJ
-FWD_FUSED_TEMPORAL = 8  # include/dstd_gcn.h DSTD_FWD_FUSED_TEMPORAL
-FWD_SEPARATE_BLOCK = 16  # include/dstd_gcn.h DSTD_FWD_SEPARATE_BLOCK
-FWD_SEPARATE_ENCODERS = 32  # include/dstd_gcn.h DSTD_FWD_SEPARATE_ENCODERS
-FWD_SEPARATE_ENDS = 64  # include/dstd_gcn.h DSTD_FWD_SEPARATE_ENDS
-KIND_FOLD, KIND_PREP, KIND_ADJ_S, KIND_SPATIAL, KIND_ADJ_T, KIND_TEMPORAL, KIND_BLOCK = range(7)
-KIND_NAMES = ("fold", "prep", "adj_spatial", "spatial_gc", "adj_temporal", "temporal_gc", "block")
-# include/dstd_gcn.h DSTD_LAUNCH_*: the kinds of a launch schedule's entries
-(LAUNCH_PREP, LAUNCH_ADJ_S, LAUNCH_SPATIAL, LAUNCH_ADJ_T, LAUNCH_TEMPORAL, LAUNCH_TEMPORAL_FUSED, LAUNCH_BLOCK,
- LAUNCH_ENC_RUN, LAUNCH_MODEL) = range(9)
 
 
 def model_schedule(B, T, V, num_feature, num_layers, flags=0, profiled=False, taps=0, cus=0):
@@ -178,174 +58,16 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"DSTD native library not built: {LIB_PATH} (run `make -C dstd-gcn_amd`)")
         L = ctypes.CDLL(LIB_PATH)
-        vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-        L.dstd_source_hash.restype = ctypes.c_char_p
-        built, tree = L.dstd_source_hash().decode(), source_hash()
         # DSTD_AB_FOREIGN_LIB=1: A/B tooling (scripts/ab_kernels.py) loading a
         # library built from an earlier revision on purpose
-        if tree is not None and built != tree and os.environ.get("DSTD_AB_FOREIGN_LIB") != "1":
+        foreign = os.environ.get("DSTD_AB_FOREIGN_LIB") == "1"
+        declare(L, allow_missing=foreign)
+        built, tree = L.dstd_source_hash().decode(), source_hash()
+        if tree is not None and built != tree and not foreign:
             raise RuntimeError(f"{LIB_PATH} was built from other sources (hash {built}, this tree {tree}): "
                                "rebuild with `make -C dstd-gcn_amd`")
-        L.dstd_version.restype = ctypes.c_char_p
-        L.dstd_error_string.restype = ctypes.c_char_p
-        L.dstd_error_string.argtypes = [ci]
-        L.dstd_dstdgc_workspace_bytes.restype = sz
-        L.dstd_dstdgc_workspace_bytes.argtypes = [ci] * 6
-        L.dstd_block_workspace_bytes.restype = sz
-        L.dstd_block_workspace_bytes.argtypes = [ci] * 5
-        L.dstd_model_workspace_bytes.restype = sz
-        L.dstd_model_workspace_bytes.argtypes = [ci] * 5
-        L.dstd_dstdgc_fwd.restype = ci
-        L.dstd_dstdgc_fwd.argtypes = [ci, vp, ci, ci, ci, ci, ci, ctypes.POINTER(GCWeights), vp, vp, vp, vp, sz, vp]
-        L.dstd_block_fwd.restype = ci
-        L.dstd_block_fwd.argtypes = [ctypes.POINTER(BlockParams), vp, ci, ci, ci, vp, vp, sz, vp]
-        L.dstd_block_fwd_ex.restype = ci
-        L.dstd_block_fwd_ex.argtypes = [ctypes.POINTER(BlockParams), vp, ci, ci, ci, vp, vp, sz, vp, ctypes.c_uint]
-        L.dstd_model_fwd.restype = ci
-        L.dstd_model_fwd.argtypes = [ctypes.POINTER(ModelParams), vp, ci, vp, vp, sz, vp]
-        L.dstd_model_fwd_ex.restype = ci
-        L.dstd_model_fwd_ex.argtypes = [ctypes.POINTER(ModelParams), vp, ci, vp, vp, sz, vp, ctypes.c_uint,
-                                        ctypes.POINTER(Profile)]
-        L.dstd_model_fwd_profiled.restype = ci
-        L.dstd_model_fwd_profiled.argtypes = [ctypes.POINTER(ModelParams), vp, ci, vp, vp, sz, vp,
-                                              ctypes.POINTER(Profile)]
-        # (absent from an earlier revision's library loaded for an A/B)
-        if hasattr(L, "dstd_model_fwd_schedule"):
-            L.dstd_model_fwd_schedule.restype = ci
-            L.dstd_model_fwd_schedule.argtypes = [ci] * 5 + [ctypes.c_uint, ci, ci, ci, ctypes.POINTER(Launch), ci]
-        L.dstd_events_create.restype = ci
-        L.dstd_events_create.argtypes = [ci, ctypes.POINTER(ctypes.c_void_p)]
-        L.dstd_events_destroy.restype = ci
-        L.dstd_events_destroy.argtypes = [ci, ctypes.POINTER(ctypes.c_void_p)]
-        L.dstd_event_elapsed_ms.restype = ci
-        L.dstd_event_elapsed_ms.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float)]
-        # training path (include/dstd_gcn_train.h)
-        u64, f32 = ctypes.c_ulonglong, ctypes.c_float
-        for n, k in (("dstd_dstdgc_train_saved_bytes", 6), ("dstd_dstdgc_train_workspace_bytes", 6),
-                     ("dstd_block_train_saved_bytes", 5), ("dstd_block_train_workspace_bytes", 5),
-                     ("dstd_model_train_saved_bytes", 5), ("dstd_model_train_workspace_bytes", 5),
-                     ("dstd_dstdgc_train_saved_bytes_r", 7), ("dstd_dstdgc_train_workspace_bytes_r", 7)):
-            getattr(L, n).restype = sz
-            getattr(L, n).argtypes = [ci] * k
-        L.dstd_dstdgc_train_fwd.restype = ci
-        L.dstd_dstdgc_train_fwd.argtypes = [ci, vp, ci, ci, ci, ci, ci, ctypes.POINTER(GCWeights), vp, vp, vp, vp, sz,
-                                            vp]
-        L.dstd_dstdgc_train_bwd.restype = ci
-        L.dstd_dstdgc_train_bwd.argtypes = [ci, vp, ci, ci, ci, ci, ci, ctypes.POINTER(GCWeights), vp, vp, sz, vp, vp,
-                                            ctypes.POINTER(GCGrads), vp, vp, vp, sz, vp]
-        L.dstd_dstdgc_train_fwd_r.restype = ci
-        L.dstd_dstdgc_train_fwd_r.argtypes = [ci, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(GCWeights), vp, vp, vp,
-                                              vp, sz, vp]
-        L.dstd_dstdgc_train_bwd_r.restype = ci
-        L.dstd_dstdgc_train_bwd_r.argtypes = [ci, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(GCWeights), vp, vp, sz,
-                                              vp, vp, ctypes.POINTER(GCGrads), vp, vp, vp, sz, vp]
-        L.dstd_block_train_fwd.restype = ci
-        L.dstd_block_train_fwd.argtypes = [ctypes.POINTER(BlockParams), vp, ci, ci, ci, f32, vp, vp, sz, vp]
-        L.dstd_block_train_bwd.restype = ci
-        L.dstd_block_train_bwd.argtypes = [ctypes.POINTER(BlockParams), vp, ci, ci, ci, vp, sz, vp, vp,
-                                           ctypes.POINTER(BlockGrads), vp, sz, vp]
-        L.dstd_model_train_fwd.restype = ci
-        L.dstd_model_train_fwd.argtypes = [ctypes.POINTER(ModelParams), vp, ci, f32, f32, u64, vp, vp, sz, vp]
-        L.dstd_model_train_bwd.restype = ci
-        L.dstd_model_train_bwd.argtypes = [ctypes.POINTER(ModelParams), vp, ci, f32, u64, vp, sz, vp,
-                                           ctypes.POINTER(ModelGrads), vp, sz, vp]
-        uf = ctypes.c_uint
-        L.dstd_block_train_fwd_ex.restype = ci
-        L.dstd_block_train_fwd_ex.argtypes = L.dstd_block_train_fwd.argtypes + [uf]
-        L.dstd_block_train_bwd_ex.restype = ci
-        L.dstd_block_train_bwd_ex.argtypes = L.dstd_block_train_bwd.argtypes + [uf]
-        L.dstd_model_train_fwd_ex.restype = ci
-        L.dstd_model_train_fwd_ex.argtypes = L.dstd_model_train_fwd.argtypes + [uf]
-        L.dstd_model_train_bwd_ex.restype = ci
-        L.dstd_model_train_bwd_ex.argtypes = [ctypes.POINTER(ModelParams), vp, ci, f32, u64, vp, sz, vp,
-                                              ctypes.POINTER(ModelGrads), vp, vp, sz, vp, uf]
-        # (absent from a round-3 library loaded for an A/B: only SyncBN calls them)
-        if hasattr(L, "dstd_bn_sync_buffer_floats"):
-            L.dstd_bn_sync_buffer_floats.restype = sz
-            L.dstd_bn_sync_buffer_floats.argtypes = [ci, ci, ci]
-            L.dstd_model_train_fwd_sync.restype = ci
-            L.dstd_model_train_fwd_sync.argtypes = L.dstd_model_train_fwd_ex.argtypes + [ctypes.POINTER(BnSyncStruct)]
-            L.dstd_model_train_bwd_sync.restype = ci
-            L.dstd_model_train_bwd_sync.argtypes = L.dstd_model_train_bwd_ex.argtypes + [ctypes.POINTER(BnSyncStruct)]
-        L.dstd_loss_workspace_bytes.restype = sz
-        L.dstd_loss_workspace_bytes.argtypes = []
-        L.dstd_mpjpe_fwd.restype = ci
-        L.dstd_mpjpe_fwd.argtypes = [vp, vp, sz, vp, vp, sz, vp]
-        L.dstd_mpjpe_bwd.restype = ci
-        L.dstd_mpjpe_bwd.argtypes = [vp, vp, sz, vp, f32, vp, vp]
-        L.dstd_frame_mpjpe.restype = ci
-        L.dstd_frame_mpjpe.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, vp, vp, ci, vp, vp]
-        # weighted / multi-term training loss (include/dstd_gcn_loss.h)
-        L.dstd_losses_workspace_bytes.restype = sz
-        L.dstd_losses_workspace_bytes.argtypes = []
-        L.dstd_losses_fwd.restype = ci
-        L.dstd_losses_fwd.argtypes = [ctypes.POINTER(LossProblem), ci, uf, vp, vp, vp, sz, vp]
-        L.dstd_losses_bwd.restype = ci
-        L.dstd_losses_bwd.argtypes = [ctypes.POINTER(LossProblem), ci, uf, vp, vp, f32, ctypes.POINTER(vp), vp]
-        # non-refine ST_GCNN_layer branch (include/dstd_gcn_aux.h)
-        L.dstd_ctg_workspace_bytes.restype = sz
-        L.dstd_ctg_workspace_bytes.argtypes = [ci] * 4
-        L.dstd_ctg_fwd.restype = ci
-        L.dstd_ctg_fwd.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]
-        L.dstd_ctg_bwd.restype = ci
-        L.dstd_ctg_bwd.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        L.dstd_conv2d_workspace_bytes.restype = sz
-        L.dstd_conv2d_workspace_bytes.argtypes = [ci] * 11
-        L.dstd_conv2d_fwd.restype = ci
-        L.dstd_conv2d_fwd.argtypes = [vp, ci, ci, ci, ci, vp, vp] + [ci] * 7 + [vp, vp, sz, vp]
-        L.dstd_conv2d_bwd.restype = ci
-        L.dstd_conv2d_bwd.argtypes = [vp, ci, ci, ci, ci, vp] + [ci] * 7 + [vp, vp, vp, vp, vp, sz, vp]
-        # adjacency / activation taps (include/dstd_gcn_taps.h; absent from
-        # an earlier revision's library loaded for an A/B)
-        if hasattr(L, "dstd_block_fwd_taps"):
-            L.dstd_block_taps_workspace_bytes.restype = sz
-            L.dstd_block_taps_workspace_bytes.argtypes = [ci] * 5
-            L.dstd_model_taps_workspace_bytes.restype = sz
-            L.dstd_model_taps_workspace_bytes.argtypes = [ci] * 5
-            L.dstd_block_fwd_taps.restype = ci
-            L.dstd_block_fwd_taps.argtypes = [ctypes.POINTER(BlockParams), vp, ci, ci, ci, vp,
-                                              ctypes.POINTER(BlockTaps), vp, sz, vp, uf]
-            L.dstd_model_fwd_taps.restype = ci
-            L.dstd_model_fwd_taps.argtypes = [ctypes.POINTER(ModelParams), vp, ci, vp, ctypes.POINTER(BlockTaps), vp,
-                                              sz, vp, uf]
-        # device-resident dataset (include/dstd_gcn_data.h; absent from an
-        # earlier revision's library loaded for an A/B)
-        if hasattr(L, "dstd_batch_gather"):
-            L.dstd_batch_gather.restype = ci
-            L.dstd_batch_gather.argtypes = [ctypes.POINTER(SeqStore), vp, ci, vp, vp, vp, vp, vp]
-        # rollout of the eval forward (include/dstd_gcn_predict.h; absent from
-        # an earlier revision's library loaded for an A/B)
-        if hasattr(L, "dstd_model_predict"):
-            L.dstd_model_predict_workspace_bytes.restype = sz
-            L.dstd_model_predict_workspace_bytes.argtypes = [ci] * 5
-            L.dstd_model_predict.restype = ci
-            L.dstd_model_predict.argtypes = [ctypes.POINTER(ModelParams), vp, ci, ci, ci, vp, vp, sz, vp, uf]
         _lib = L
     return _lib
-
-
-EXPORTS = ("dstd_version", "dstd_source_hash", "dstd_error_string", "dstd_dstdgc_workspace_bytes", "dstd_block_workspace_bytes",
-           "dstd_model_workspace_bytes", "dstd_dstdgc_fwd", "dstd_block_fwd", "dstd_model_fwd",
-           "dstd_model_fwd_profiled", "dstd_events_create", "dstd_events_destroy", "dstd_event_elapsed_ms",
-           "dstd_block_fwd_ex", "dstd_model_fwd_ex", "dstd_model_fwd_schedule")
-TRAIN_EXPORTS = ("dstd_dstdgc_train_saved_bytes", "dstd_dstdgc_train_workspace_bytes", "dstd_dstdgc_train_fwd",
-                 "dstd_dstdgc_train_bwd", "dstd_block_train_saved_bytes", "dstd_block_train_workspace_bytes",
-                 "dstd_block_train_fwd", "dstd_block_train_bwd", "dstd_model_train_saved_bytes",
-                 "dstd_model_train_workspace_bytes", "dstd_model_train_fwd", "dstd_model_train_bwd",
-                 "dstd_loss_workspace_bytes", "dstd_mpjpe_fwd", "dstd_mpjpe_bwd", "dstd_frame_mpjpe",
-                 "dstd_block_train_fwd_ex", "dstd_block_train_bwd_ex", "dstd_model_train_fwd_ex",
-                 "dstd_model_train_bwd_ex", "dstd_dstdgc_train_saved_bytes_r",
-                 "dstd_dstdgc_train_workspace_bytes_r", "dstd_dstdgc_train_fwd_r", "dstd_dstdgc_train_bwd_r",
-                 "dstd_bn_sync_buffer_floats", "dstd_model_train_fwd_sync", "dstd_model_train_bwd_sync",
-                 "dstd_debug_aggb_last", "dstd_debug_bn_last")
-AUX_EXPORTS = ("dstd_ctg_workspace_bytes", "dstd_ctg_fwd", "dstd_ctg_bwd", "dstd_conv2d_workspace_bytes",
-               "dstd_conv2d_fwd", "dstd_conv2d_bwd")
-LOSS_EXPORTS = ("dstd_losses_workspace_bytes", "dstd_losses_fwd", "dstd_losses_bwd")
-TAPS_EXPORTS = ("dstd_block_taps_workspace_bytes", "dstd_model_taps_workspace_bytes", "dstd_block_fwd_taps",
-                "dstd_model_fwd_taps")
-DATA_EXPORTS = ("dstd_batch_gather",)
-PREDICT_EXPORTS = ("dstd_model_predict_workspace_bytes", "dstd_model_predict")
-PREDICT_MAX_WINDOWS = 64  # include/dstd_gcn_predict.h DSTD_PREDICT_MAX_WINDOWS
 
 
 ARITHMETICS = ("split", "fp32")
