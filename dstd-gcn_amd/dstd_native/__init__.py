@@ -1,4 +1,4 @@
-"""ctypes binding of the MI355X C ABI (include/*.h; declared in abi.py).
+"""ctypes binding of the MI355X C ABI (include/*.h, declared in abi.py; include/ext/*.h in ext.py).
 
 The shared library ``libdstd_gcn.so`` is built in-tree (``make -C dstd-gcn_amd``
 or ``__graft_entry__.build()``).  There is no fallback: if the library is
@@ -10,6 +10,7 @@ import os
 import torch
 
 from .abi import *  # noqa: F401,F403 -- the constants, structs and export lists are this package's names
+from . import ext  # include/ext/*.h: a table of its own, by name only (not star-imported)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DSTD_LIB overrides the library (A/B experiments with variant builds)
@@ -36,7 +37,7 @@ def source_hash():
     import glob
     import hashlib
     pkg = os.path.dirname(_HERE)
-    rel = [os.path.relpath(p, pkg) for pat in ("csrc/*.hip", "csrc/*.h", "../include/*.h")
+    rel = [os.path.relpath(p, pkg) for pat in ("csrc/*.hip", "csrc/*.h", "../include/*.h", "../include/ext/*.h")
            for p in glob.glob(os.path.join(pkg, pat))]
     files = sorted(rel) + ["Makefile"]
     h = hashlib.sha256()
@@ -61,7 +62,7 @@ def lib():
         # DSTD_AB_FOREIGN_LIB=1: A/B tooling (scripts/ab_kernels.py) loading a
         # library built from an earlier revision on purpose
         foreign = os.environ.get("DSTD_AB_FOREIGN_LIB") == "1"
-        declare(L, allow_missing=foreign)
+        declare(L, allow_missing=foreign, extra=ext.ABI)
         built, tree = L.dstd_source_hash().decode(), source_hash()
         if tree is not None and built != tree and not foreign:
             raise RuntimeError(f"{LIB_PATH} was built from other sources (hash {built}, this tree {tree}): "

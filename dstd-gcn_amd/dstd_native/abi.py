@@ -214,12 +214,13 @@ ABI = {
 del i, u, f, z, p, ll, u64, GW, GG, BP, BG, BT, MP, MG, PR, SY, LP  # shorthand of this file only
 
 
-def declare(L, allow_missing=False):
-    """Give every entry point of ABI its restype and argtypes on the loaded
+def declare(L, allow_missing=False, extra=None):
+    """Give every entry point of ABI -- and of ``extra``, a table of the same
+    form (dstd_native.ext.ABI) -- its restype and argtypes on the loaded
     library L.  The one rule for a symbol L does not export: it is an error,
     unless allow_missing (an earlier revision's library loaded on purpose),
     when it is skipped."""
-    for header, protos in ABI.items():
+    for header, protos in (*ABI.items(), *(extra or {}).items()):
         for name, (restype, argtypes) in protos.items():
             try:
                 fn = getattr(L, name)

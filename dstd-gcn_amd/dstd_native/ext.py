@@ -1,0 +1,56 @@
+"""The C ABI of include/ext/*.h, declared once as abi.py declares include/*.h.
+
+A table of its own: tests/test_abi_host.py pins the key set and the sizes of
+abi.ABI / abi.C_TYPES, so this module adds nothing to either and is not
+star-imported into dstd_native (``dstd_native.ext`` names it).  lib() hands
+ABI below to abi.declare with abi.ABI: one loop, one rule for a missing symbol.
+
+The extension headers bring no typedef, so C_TYPES is empty, and this
+namespace holds no Structure class: the reader that compares a header with its
+binding (tests/abi_reader.py) resolves struct names through the C_TYPES of the
+binding it is given.  A pointer to a struct of include/*.h is therefore
+declared as void* here; callers pass the abi.py Structure itself (the
+wrappers below take it by reference), whose layout tests/test_abi_host.py
+settles.
+"""
+import ctypes
+
+from . import abi
+
+C_TYPES = {}
+
+_i, _u, _f, _z, _p = ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
+
+ABI = {
+    "ext/dstd_gcn_rollout.h": {
+        "dstd_model_rollout_saved_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
+        "dstd_model_rollout_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+        # (p, obs, B, input_n, horizon, momentum, dropout_p, seeds, out, saved, saved_bytes, stream, flags)
+        "dstd_model_rollout_fwd": (_i, [_p, _p, _i, _i, _i, _f, _f, _p, _p, _p, _z, _p, _u]),
+        # (p, B, input_n, horizon, dropout_p, seeds, saved, saved_bytes, dout, g, dobs, workspace,
+        #  workspace_bytes, stream, flags)
+        "dstd_model_rollout_bwd": (_i, [_p, _i, _i, _i, _f, _p, _p, _z, _p, _p, _p, _p, _z, _p, _u]),
+        # (p, B, input_n, horizon, k, ... as dstd_model_rollout_bwd)
+        "dstd_model_rollout_bwd_window": (_i, [_p, _i, _i, _i, _i, _f, _p, _p, _z, _p, _p, _p, _p, _z, _p, _u]),
+        # (step, dout, Gn, dst, B, T, input_n, V, horizon, k, stream)
+        "dstd_model_rollout_glue_bwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    },
+}
+
+ROLLOUT_EXPORTS = tuple(ABI["ext/dstd_gcn_rollout.h"])
+
+
+def struct_ref(s, cls):
+    """``s`` (an abi.py Structure of class ``cls``) as the void* argument of an
+    entry point above; anything else is a TypeError here, not a crash there."""
+    if not isinstance(s, cls):
+        raise TypeError(f"expected {cls.__name__}, got {type(s).__name__}")
+    return ctypes.byref(s)
+
+
+def model_params_ref(p):
+    return struct_ref(p, abi.ModelParams)
+
+
+def model_grads_ref(g):
+    return struct_ref(g, abi.ModelGrads)

@@ -188,7 +188,19 @@ class PredictionEngine:
         return optimizer, scheduler
 
     # ------------------------------------------------------------------
-    def train(self, train_loader, epoch, time_tsfm=None, scale_tsfm=None, weights=None, max_iter=-1):
+    def train(self, train_loader, epoch, time_tsfm=None, scale_tsfm=None, weights=None, max_iter=-1, horizon=None):
+        """``horizon`` (None: the reference's path, one forward of the padded
+        window): train through a rollout instead -- the first
+        ``input_time_frame`` frames of ``inputs`` (and of ``inputs_inv``) are the
+        observations, ``model.rollout`` / ``rollout_pair`` predicts the
+        ``horizon`` frames after them as one differentiable native chain, and
+        every batch must hold ``input_time_frame + horizon`` frames
+        (``DeviceSequences.from_windows(..., output_n=horizon)``).  Losses,
+        gradient all-reduce, clip and Adam are those of the plain step;
+        ``learn.graph`` steps run eagerly."""
+        if horizon is not None and time_tsfm is not None:
+            raise ValueError("train: a time transform of a window does not chain over windows; "
+                             "horizon needs time_tsfm=None")
         dev = self.device
         t_l = {key_loss: DeviceAccum(dev) for key_loss in self.config["loss"]}
         self.model.train()
@@ -201,7 +213,7 @@ class PredictionEngine:
         if self._graph_step is not None and key != self._graph_weights_key:
             self._graph_step = None  # captured without joint weights, or with another buffer: capture again
         self._graph_weights_key = key
-        if self.model.fused_losses(weights):
+        if self.model.fused_losses(weights) or horizon is not None:
             self.model.loss_spec.matrix(dev)
         # backward accumulates straight into .grad (dstd_native.grad_sink) for
         # this epoch's steps only: the flag is restored on the way out, so a
@@ -211,11 +223,11 @@ class PredictionEngine:
         prev_inplace = getattr(net, "_dstd_inplace_grads", False)
         net._dstd_inplace_grads = True
         try:
-            return self._train_epoch(train_loader, epoch, time_tsfm, scale_tsfm, weights, max_iter, t_l)
+            return self._train_epoch(train_loader, epoch, time_tsfm, scale_tsfm, weights, max_iter, t_l, horizon)
         finally:
             net._dstd_inplace_grads = prev_inplace
 
-    def _train_epoch(self, train_loader, epoch, time_tsfm, scale_tsfm, weights, max_iter, t_l):
+    def _train_epoch(self, train_loader, epoch, time_tsfm, scale_tsfm, weights, max_iter, t_l, horizon=None):
         dev = self.device
         distributed = _world()[1] > 1
         num_iter = len(train_loader) if max_iter == -1 else min(len(train_loader), max_iter)
@@ -224,10 +236,12 @@ class PredictionEngine:
             N = inputs[0].shape[0] if isinstance(inputs, list) else inputs.shape[0]
 
             def step(inp, inp_inv, targ):
+                if horizon is not None:
+                    return self._step_rollout(inp, inp_inv, targ, horizon, scale_tsfm, weights, distributed)
                 return self._step(inp, inp_inv, targ, time_tsfm, scale_tsfm, weights, distributed)
 
             tensors = not isinstance(inputs, list) and torch.is_tensor(inputs_inv)
-            if self._graphed() and tensors:
+            if self._graphed() and tensors and horizon is None:
                 g = self._graph_step
                 if g is None:
                     from .graphed import GraphedStep
@@ -324,6 +338,47 @@ class PredictionEngine:
                 for ls in loss_inv:
                     all_loss = all_loss + loss_inv[ls]
                 all_loss = all_loss / 2
+        self.optimizer.zero_grad()
+        all_loss.backward()
+        if distributed:
+            from dstd_dist import allreduce_grads
+            allreduce_grads(self.model.parameters())
+        if self.config.get("clip", -1) > 0:
+            nn.utils.clip_grad_norm_(self.model.model.parameters(), max_norm=self.config["clip"])
+        self.optimizer.step()
+        return tuple(loss[ls].detach() for ls in self.config["loss"])
+
+    def _step_rollout(self, inputs, inputs_inv, targets, horizon, scale_tsfm, weights, distributed):
+        """One training step through a rollout (train(horizon=...)): the
+        observed frames of the batch (and of its time reversal) rolled out
+        ``horizon`` frames by one native chain, every loss line of both passes
+        in one native forward / backward against the frames that follow the
+        observations -- targets[:, input_n:] is (input_n, +1), the reversal's
+        targets.flip(1)[:, input_n:] is (horizon - 1, -1) -- then backward,
+        gradient all-reduce / clip and Adam as ``_step``."""
+        net = self.model.model
+        input_n = net.input_time_frame
+        pair = bool(self.config["inverse"])
+        if isinstance(inputs, list) or (pair and not torch.is_tensor(inputs_inv)):
+            raise ValueError("train: horizon takes one input tensor per batch, not a list")
+        if not hasattr(net, "rollout"):
+            raise NotImplementedError(f"train: horizon needs a model with rollout ({type(net).__name__} has none)")
+        for name, x in (("inputs", inputs), ("inputs_inv", inputs_inv if pair else inputs), ("targets", targets)):
+            if x.shape[1] != input_n + horizon:
+                raise ValueError(f"train: horizon {horizon} after {input_n} observed frames needs {name} of "
+                                 f"{input_n + horizon} frames, got {x.shape[1]}")
+        observed = self.transform(inputs)[:, :input_n].contiguous()
+        if pair:
+            observed_inv = self.transform(inputs_inv)[:, :input_n].contiguous()
+            preds = [self.inverse(o) for o in net.rollout_pair(observed, observed_inv, horizon)]
+            maps = [(input_n, 1), (horizon - 1, -1)]
+        else:
+            preds, maps = [self.inverse(net.rollout(observed, horizon))], [(input_n, 1)]
+        if scale_tsfm is not None:
+            preds = [scale_tsfm.inverse(o) for o in preds]
+        out = weighted_losses(self.model.loss_spec, preds, targets, maps, weights)
+        all_loss = out.sum() / 2 if pair else out.sum()
+        loss = dict(zip(self.config["loss"], out[0].unbind(0)))
         self.optimizer.zero_grad()
         all_loss.backward()
         if distributed:

@@ -567,6 +567,139 @@ class _ModelTrainPair(torch.autograd.Function):
         return _ModelTrain.backward(ctx, torch.cat([d1, d2]))
 
 
+def _param_hooks(params):
+    return any(p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None) for p in params)
+
+
+class _RolloutTrain(torch.autograd.Function):
+    """DSTDGCN.rollout under autograd: the whole chain of train forwards as one
+    native call and its backward as another (include/ext/dstd_gcn_rollout.h).
+    Built like _ModelTrain -- flags, device seeds, the anchored parameters and
+    the in-place gradient arena -- but eager only: there is no custom op for
+    the chain, so both directions call the C ABI directly."""
+
+    @staticmethod
+    def forward(ctx, model, paired, horizon, obs, *params):
+        L = native.lib()
+        n, tin, v, c = obs.shape
+        dev = obs.device
+        t = tin + model.output_time_frame
+        windows = -(-horizon // model.output_time_frame)
+        flags = _bn_flags(model) | (native.TRAIN_PAIRED if paired else 0)
+        if getattr(model, "_dstd_one_stream", False):
+            flags |= native.TRAIN_ONE_STREAM
+        drop = float(model.do_in.p) if model.do_in.training else 0.0
+        seeds, ctx.seed_t = None, None
+        if drop > 0:
+            # one device seed per window, drawn in one launch and read there
+            # (DSTD_TRAIN_SEED_DEVICE); kept until the backward has regenerated the masks
+            ctx.seed_t = torch.randint(0, 2 ** 62, (windows,), device=dev, dtype=torch.int64)
+            seeds = ctx.seed_t.data_ptr()
+            flags |= native.TRAIN_SEED_DEVICE
+        params_all, buffers = model._tree.get(model)
+        out = obs.new_empty(n, horizon, v, c)
+        nbytes = L.dstd_model_rollout_saved_bytes(n, t, v, model.num_feature, model.num_layers, windows)
+        saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        code = L.dstd_model_rollout_fwd(native.ext.model_params_ref(model._native_params()), native.ptr(obs, "observed"),
+                                        n, tin, horizon, _bn_momentum(model), drop, seeds, native.ptr(out, "out"),
+                                        saved.data_ptr(), nbytes, native.stream_handle(dev), flags)
+        native.check(code, "dstd_model_rollout_fwd")
+        if not flags & native.TRAIN_RUNNING_STATS:
+            # the running statistics were updated once per window (twice when paired)
+            torch.autograd.graph.increment_version(buffers)
+            _count_batch(model, windows * (2 if paired else 1))
+        ctx.model, ctx.saved_buf, ctx.drop, ctx.flags, ctx.shape = model, saved, drop, flags, (n, tin, v, c)
+        ctx.horizon = horizon
+        ctx.anchored = len(params) == 1 and params[0] is getattr(model, "_dstd_anchor_t", None)
+        ctx.params = params_all if ctx.anchored else list(params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = native.lib()
+        model = ctx.model
+        n, tin, v, c = ctx.shape
+        dev = dout.device
+        dout = dout.contiguous()
+        need_dx = bool(ctx.needs_input_grad[3])
+        if ctx.saved_buf is None:
+            raise RuntimeError("DSTDGCN.rollout: backward through the chain a second time "
+                               "(its saved windows were freed by the first)")
+        arena, direct = None, False
+        if ctx.anchored or (getattr(model, "_dstd_inplace_grads", False) and not _param_hooks(ctx.params)):
+            arena, direct = native.grad_sink(model, ctx.params, dev)
+        t = tin + model.output_time_frame
+        windows = -(-ctx.horizon // model.output_time_frame)
+        ws = native.workspace(dev, L.dstd_model_rollout_workspace_bytes(n, t, v, model.num_feature, model.num_layers))
+        dobs = dout.new_empty(n, tin, v, c) if need_dx else None
+        pref = native.ext.model_params_ref(model._native_params())
+        tail = (ctx.drop, ctx.seed_t.data_ptr() if ctx.seed_t is not None else None, ctx.saved_buf.data_ptr(),
+                ctx.saved_buf.numel(), native.ptr(dout, "dout"))
+        tail2 = (dobs.data_ptr() if need_dx else None, ws.data_ptr(), ws.numel(), native.stream_handle(dev), ctx.flags)
+        if direct:
+            # every window accumulates (+=) into the parameters' .grad, as the K
+            # backwards of a loop do in this mode: one native call
+            g = getattr(arena, "model_grads", None)
+            if g is None:
+                g = arena.model_grads = model._native_grads(arena)
+            code = L.dstd_model_rollout_bwd(pref, n, tin, ctx.horizon, *tail, native.ext.model_grads_ref(g), *tail2)
+            native.check(code, "dstd_model_rollout_bwd")
+        else:
+            # gradients for autograd: a zeroed arena per window, summed in backward
+            # order (window K-1 first) -- what autograd makes of the K backwards of
+            # a loop, each of which returns an arena of its own.  One (+=) chain
+            # into a single arena would round alpha_sm, which both spatial
+            # operators of a block add into, differently from that.
+            numel = native.arena_numel(ctx.params)
+            bufs = torch.zeros(windows, numel, dtype=torch.float32, device=dev)
+            for k in range(windows - 1, -1, -1):
+                g = model._native_grads(native.GradArena(ctx.params, dev, buf=bufs[k]))
+                code = L.dstd_model_rollout_bwd_window(pref, n, tin, ctx.horizon, k, *tail,
+                                                       native.ext.model_grads_ref(g), *tail2)
+                native.check(code, "dstd_model_rollout_bwd_window")
+            total = bufs[windows - 1]
+            for k in range(windows - 2, -1, -1):
+                total += bufs[k]
+            arena = native.GradArena(ctx.params, dev, buf=total)
+        ctx.saved_buf = ctx.seed_t = None
+        if direct:
+            return (None, None, None, dobs, *([None] * (1 if ctx.anchored else len(arena.params))))
+        if ctx.anchored:
+            # .grad was set by someone else since the forward (_ModelTrain.backward)
+            for p, gv in zip(arena.params, arena.views()):
+                if gv is not None and p.requires_grad:
+                    if p.grad is None:
+                        p.grad = gv.clone()
+                    else:
+                        p.grad.add_(gv)
+            return (None, None, None, dobs, None)
+        return (None, None, None, dobs, *arena.views())
+
+
+class _RolloutTrainPair(torch.autograd.Function):
+    """DSTDGCN.rollout_pair's Function: _RolloutTrain over the concatenated
+    pair (DSTD_TRAIN_PAIRED) with the two halves as two outputs, as
+    _ModelTrainPair."""
+
+    @staticmethod
+    def forward(ctx, model, n, horizon, obs, *params):
+        out = _RolloutTrain.forward(ctx, model, True, horizon, obs, *params)
+        ctx.half = n
+        return out[:n], out[n:]
+
+    @staticmethod
+    def backward(ctx, d1, d2):
+        n2, tin, v, c = ctx.shape
+        n = ctx.half
+        ref = d1 if d1 is not None else d2
+        if d1 is None:
+            d1 = ref.new_zeros((n, ctx.horizon, v, c))
+        if d2 is None:
+            d2 = ref.new_zeros((n2 - n, ctx.horizon, v, c))
+        # (argument positions: model, n, horizon, obs, params -- as _RolloutTrain's model, paired, horizon, obs, params)
+        return _RolloutTrain.backward(ctx, torch.cat([d1, d2]))
+
+
 class BatchNorm(nn.Module):
     """BN1d over C*V channels of an NCTV tensor (reference :35-50).  Glue only:
     on the hot path every BatchNorm is folded into a kernel epilogue."""
@@ -1165,6 +1298,78 @@ class DSTDGCN(_NativeModule):
         code = L.dstd_model_predict(p, native.ptr(obs, "observed"), n, tin, out.shape[1], native.ptr(out, "out"),
                                     ws.data_ptr(), ws.numel(), native.stream_handle(dev), flags)
         native.check(code, "dstd_model_predict")
+
+    def _rollout_args(self, observed, horizon, what):
+        """(observed's shape, horizon) of a rollout call, checked as ``predict`` checks them."""
+        n, tin, v, c = observed.shape
+        assert tin == self.input_time_frame
+        if c != self.input_channels // 2 or v != self.joints_to_consider:
+            raise ValueError(f"DSTDGCN: expected [N, {tin}, {self.joints_to_consider}, {self.input_channels // 2}], "
+                             f"got {list(observed.shape)}")
+        horizon = self.output_time_frame if horizon is None else int(horizon)
+        if horizon < 1:
+            raise ValueError(f"DSTDGCN.{what}: horizon {horizon} < 1")
+        if -(-horizon // self.output_time_frame) > native.PREDICT_MAX_WINDOWS:
+            raise ValueError(f"DSTDGCN.{what}: horizon {horizon} needs more than {native.PREDICT_MAX_WINDOWS} "
+                             f"windows of {self.output_time_frame} frames")
+        return (n, tin, v, c), horizon
+
+    def _rollout_refusals(self, observed, what):
+        """What the differentiable chain does not cover, said before anything runs."""
+        if self.training and self.__dict__.get("_dstd_bn_sync") is not None:
+            raise NotImplementedError(f"DSTDGCN.{what}: no cross-rank BatchNorm through a rollout "
+                                      "(include/ext/dstd_gcn_rollout.h has no dstd_bn_sync variant)")
+        if type(observed) is not torch.Tensor or torch.compiler.is_compiling():
+            raise RuntimeError(f"DSTDGCN.{what}: eager only -- the chain has no custom op, so it cannot be traced "
+                               "(torch.compile, tensor subclasses)")
+        native.lib()
+        native.require_device(observed, "observed")
+
+    def rollout(self, observed, horizon=None):
+        """``predict`` that autograd can differentiate and a train-mode model
+        can run: the ``horizon`` frames (default ``output_time_frame``) after
+        ``observed`` [N, input_time_frame, V, 3], as [N, horizon, V, 3].
+
+        In ``eval()`` mode with nothing to differentiate it is
+        ``self.predict(observed, horizon)``.  In ``train()`` mode every window
+        is the train-mode forward -- batch statistics per window, the running
+        statistics updated once per window in window order, a dropout mask per
+        window -- and in ``eval()`` mode with grad enabled and ``observed`` or a
+        parameter requiring grad it is the eval forward under autograd
+        (BatchNorm on its running statistics, no dropout).  Either way the
+        chain is ONE autograd Function over two native calls
+        (include/ext/dstd_gcn_rollout.h): what a loop of ``self(x_k)`` over
+        windows built under autograd computes -- outputs, buffers and
+        gradients bit for bit (tests/test_gpu_rollout.py) -- without K
+        Functions of ~300 inputs each, and with the gradient of the window
+        shuffling summed in a fixed order.  Eager only; no cross-rank
+        BatchNorm."""
+        (n, tin, v, c), horizon = self._rollout_args(observed, horizon, "rollout")
+        params = self._tree.get(self)[0]
+        if not self.training and not _needs_grad(observed, *params):
+            return self.predict(observed, horizon)
+        self._rollout_refusals(observed, "rollout")
+        observed = observed.contiguous()
+        if n == 0:  # empty batch: empty output
+            return _mark(observed.new_empty(0, horizon, v, c), observed, *params)
+        return _RolloutTrain.apply(self, False, horizon, observed, *_anchor_of(self, observed, params))
+
+    def rollout_pair(self, obs1, obs2, horizon=None):
+        """``(self.rollout(obs1, horizon), self.rollout(obs2, horizon))`` as one
+        chain over the concatenated batch, as ``forward_pair`` is for one
+        window: in train mode every window keeps each half's own batch
+        statistics and the running statistics take obs1's update then obs2's
+        (DSTD_TRAIN_PAIRED), window by window.  Elsewhere (eval, shapes that
+        differ, an empty batch) it is the two calls."""
+        if not self.training or obs1.shape != obs2.shape or obs1.shape[0] == 0 or obs1.device != obs2.device:
+            return self.rollout(obs1, horizon), self.rollout(obs2, horizon)
+        (n, tin, v, c), horizon = self._rollout_args(obs1, horizon, "rollout_pair")
+        self._rollout_refusals(obs1, "rollout_pair")
+        if type(obs2) is not torch.Tensor:
+            raise RuntimeError("DSTDGCN.rollout_pair: eager only (tensor subclasses cannot be traced through the chain)")
+        obs = torch.cat([obs1, obs2]).contiguous()
+        params = self._tree.get(self)[0]
+        return _RolloutTrainPair.apply(self, n, horizon, obs, *_anchor_of(self, obs, params))
 
     def forward_pair(self, x1, x2):
         """``(self(x1), self(x2))`` -- PredictionEngine.train's forward of a
