@@ -62,7 +62,7 @@ def lib():
         # DSTD_AB_FOREIGN_LIB=1: A/B tooling (scripts/ab_kernels.py) loading a
         # library built from an earlier revision on purpose
         foreign = os.environ.get("DSTD_AB_FOREIGN_LIB") == "1"
-        declare(L, allow_missing=foreign, extra=ext.ABI)
+        declare(L, allow_missing=foreign, extra=ext.ALL)
         built, tree = L.dstd_source_hash().decode(), source_hash()
         if tree is not None and built != tree and not foreign:
             raise RuntimeError(f"{LIB_PATH} was built from other sources (hash {built}, this tree {tree}): "

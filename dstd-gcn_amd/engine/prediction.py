@@ -188,7 +188,8 @@ class PredictionEngine:
         return optimizer, scheduler
 
     # ------------------------------------------------------------------
-    def train(self, train_loader, epoch, time_tsfm=None, scale_tsfm=None, weights=None, max_iter=-1, horizon=None):
+    def train(self, train_loader, epoch, time_tsfm=None, scale_tsfm=None, weights=None, max_iter=-1, horizon=None,
+              teacher_ratio=0.0):
         """``horizon`` (None: the reference's path, one forward of the padded
         window): train through a rollout instead -- the first
         ``input_time_frame`` frames of ``inputs`` (and of ``inputs_inv``) are the
@@ -197,10 +198,23 @@ class PredictionEngine:
         every batch must hold ``input_time_frame + horizon`` frames
         (``DeviceSequences.from_windows(..., output_n=horizon)``).  Losses,
         gradient all-reduce, clip and Adam are those of the plain step;
-        ``learn.graph`` steps run eagerly."""
+        ``learn.graph`` steps run eagerly.
+
+        ``teacher_ratio`` (with ``horizon``; 0: free running, the step as it
+        is without the argument): scheduled sampling.  At every window
+        boundary each sample of the batch (and of its time reversal) is given
+        the ground-truth frames of ``targets`` as its next window with this
+        probability, drawn on the device from torch's generator, and no
+        gradient crosses such a boundary.  It holds for this call: anneal it
+        from 1 towards 0 over the epochs."""
         if horizon is not None and time_tsfm is not None:
             raise ValueError("train: a time transform of a window does not chain over windows; "
                              "horizon needs time_tsfm=None")
+        teacher_ratio = float(teacher_ratio)
+        if not 0.0 <= teacher_ratio <= 1.0:
+            raise ValueError(f"train: teacher_ratio {teacher_ratio} is outside [0, 1]")
+        if teacher_ratio > 0 and horizon is None:
+            raise ValueError("train: teacher_ratio forces windows of a rollout; it needs horizon")
         dev = self.device
         t_l = {key_loss: DeviceAccum(dev) for key_loss in self.config["loss"]}
         self.model.train()
@@ -223,11 +237,13 @@ class PredictionEngine:
         prev_inplace = getattr(net, "_dstd_inplace_grads", False)
         net._dstd_inplace_grads = True
         try:
-            return self._train_epoch(train_loader, epoch, time_tsfm, scale_tsfm, weights, max_iter, t_l, horizon)
+            return self._train_epoch(train_loader, epoch, time_tsfm, scale_tsfm, weights, max_iter, t_l, horizon,
+                                     teacher_ratio)
         finally:
             net._dstd_inplace_grads = prev_inplace
 
-    def _train_epoch(self, train_loader, epoch, time_tsfm, scale_tsfm, weights, max_iter, t_l, horizon=None):
+    def _train_epoch(self, train_loader, epoch, time_tsfm, scale_tsfm, weights, max_iter, t_l, horizon=None,
+                     teacher_ratio=0.0):
         dev = self.device
         distributed = _world()[1] > 1
         num_iter = len(train_loader) if max_iter == -1 else min(len(train_loader), max_iter)
@@ -237,7 +253,8 @@ class PredictionEngine:
 
             def step(inp, inp_inv, targ):
                 if horizon is not None:
-                    return self._step_rollout(inp, inp_inv, targ, horizon, scale_tsfm, weights, distributed)
+                    return self._step_rollout(inp, inp_inv, targ, horizon, scale_tsfm, weights, distributed,
+                                              *((teacher_ratio,) if teacher_ratio > 0 else ()))
                 return self._step(inp, inp_inv, targ, time_tsfm, scale_tsfm, weights, distributed)
 
             tensors = not isinstance(inputs, list) and torch.is_tensor(inputs_inv)
@@ -348,14 +365,17 @@ class PredictionEngine:
         self.optimizer.step()
         return tuple(loss[ls].detach() for ls in self.config["loss"])
 
-    def _step_rollout(self, inputs, inputs_inv, targets, horizon, scale_tsfm, weights, distributed):
+    def _step_rollout(self, inputs, inputs_inv, targets, horizon, scale_tsfm, weights, distributed, teacher_ratio=0.0):
         """One training step through a rollout (train(horizon=...)): the
         observed frames of the batch (and of its time reversal) rolled out
         ``horizon`` frames by one native chain, every loss line of both passes
         in one native forward / backward against the frames that follow the
         observations -- targets[:, input_n:] is (input_n, +1), the reversal's
         targets.flip(1)[:, input_n:] is (horizon - 1, -1) -- then backward,
-        gradient all-reduce / clip and Adam as ``_step``."""
+        gradient all-reduce / clip and Adam as ``_step``.  ``teacher_ratio`` > 0:
+        scheduled sampling -- a mask [windows, samples of both passes] drawn on
+        the device (no synchronisation) and ``targets`` as the teacher of both
+        passes, the reversal reading it backwards."""
         net = self.model.model
         input_n = net.input_time_frame
         pair = bool(self.config["inverse"])
@@ -368,12 +388,17 @@ class PredictionEngine:
                 raise ValueError(f"train: horizon {horizon} after {input_n} observed frames needs {name} of "
                                  f"{input_n + horizon} frames, got {x.shape[1]}")
         observed = self.transform(inputs)[:, :input_n].contiguous()
+        tf = {}
+        if teacher_ratio > 0:
+            windows = -(-horizon // net.output_time_frame)
+            drawn = torch.rand(windows, observed.shape[0] * (2 if pair else 1), device=observed.device)
+            tf = dict(teacher=self.transform(targets), teacher_mask=drawn < teacher_ratio)
         if pair:
             observed_inv = self.transform(inputs_inv)[:, :input_n].contiguous()
-            preds = [self.inverse(o) for o in net.rollout_pair(observed, observed_inv, horizon)]
+            preds = [self.inverse(o) for o in net.rollout_pair(observed, observed_inv, horizon, **tf)]
             maps = [(input_n, 1), (horizon - 1, -1)]
         else:
-            preds, maps = [self.inverse(net.rollout(observed, horizon))], [(input_n, 1)]
+            preds, maps = [self.inverse(net.rollout(observed, horizon, **tf))], [(input_n, 1)]
         if scale_tsfm is not None:
             preds = [scale_tsfm.inverse(o) for o in preds]
         out = weighted_losses(self.model.loss_spec, preds, targets, maps, weights)

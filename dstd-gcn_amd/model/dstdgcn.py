@@ -700,6 +700,127 @@ class _RolloutTrainPair(torch.autograd.Function):
         return _RolloutTrain.backward(ctx, torch.cat([d1, d2]))
 
 
+class _RolloutTeacher(torch.autograd.Function):
+    """_RolloutTrain with scheduled sampling (include/ext/dstd_gcn_teacher.h):
+    the same two native calls through the _tf_ entry points, which take the
+    teacher's frames, one (t0, step) frame map per half and the mask.  The mask
+    stays in ctx, since the backward reads it again; the teacher and the mask
+    get no gradient.  saved, workspace, arenas and what is returned to autograd
+    are _RolloutTrain's."""
+
+    @staticmethod
+    def forward(ctx, model, paired, horizon, obs, teacher, mask, maps, *params):
+        L = native.lib()
+        n, tin, v, c = obs.shape
+        dev = obs.device
+        t = tin + model.output_time_frame
+        windows = -(-horizon // model.output_time_frame)
+        flags = _bn_flags(model) | (native.TRAIN_PAIRED if paired else 0)
+        if getattr(model, "_dstd_one_stream", False):
+            flags |= native.TRAIN_ONE_STREAM
+        drop = float(model.do_in.p) if model.do_in.training else 0.0
+        seeds, ctx.seed_t = None, None
+        if drop > 0:
+            ctx.seed_t = torch.randint(0, 2 ** 62, (windows,), device=dev, dtype=torch.int64)
+            seeds = ctx.seed_t.data_ptr()
+            flags |= native.TRAIN_SEED_DEVICE
+        params_all, buffers = model._tree.get(model)
+        out = obs.new_empty(n, horizon, v, c)
+        nbytes = L.dstd_model_rollout_saved_bytes(n, t, v, model.num_feature, model.num_layers, windows)
+        saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ctx.mask = mask
+        ctx.tf = (native.ptr(teacher, "teacher"), teacher.shape[1], *native.ext.frame_maps(maps), mask.data_ptr())
+        code = L.dstd_model_rollout_tf_fwd(native.ext.model_params_ref(model._native_params()),
+                                           native.ptr(obs, "observed"), n, tin, horizon, _bn_momentum(model), drop,
+                                           seeds, native.ptr(out, "out"), saved.data_ptr(), nbytes, *ctx.tf,
+                                           native.stream_handle(dev), flags)
+        native.check(code, "dstd_model_rollout_tf_fwd")
+        if not flags & native.TRAIN_RUNNING_STATS:
+            torch.autograd.graph.increment_version(buffers)
+            _count_batch(model, windows * (2 if paired else 1))
+        ctx.model, ctx.saved_buf, ctx.drop, ctx.flags, ctx.shape = model, saved, drop, flags, (n, tin, v, c)
+        ctx.horizon = horizon
+        ctx.anchored = len(params) == 1 and params[0] is getattr(model, "_dstd_anchor_t", None)
+        ctx.params = params_all if ctx.anchored else list(params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = native.lib()
+        model = ctx.model
+        n, tin, v, c = ctx.shape
+        dev = dout.device
+        dout = dout.contiguous()
+        need_dx = bool(ctx.needs_input_grad[3])
+        if ctx.saved_buf is None:
+            raise RuntimeError("DSTDGCN.rollout: backward through the chain a second time "
+                               "(its saved windows were freed by the first)")
+        arena, direct = None, False
+        if ctx.anchored or (getattr(model, "_dstd_inplace_grads", False) and not _param_hooks(ctx.params)):
+            arena, direct = native.grad_sink(model, ctx.params, dev)
+        t = tin + model.output_time_frame
+        windows = -(-ctx.horizon // model.output_time_frame)
+        ws = native.workspace(dev, L.dstd_model_rollout_workspace_bytes(n, t, v, model.num_feature, model.num_layers))
+        dobs = dout.new_empty(n, tin, v, c) if need_dx else None
+        pref = native.ext.model_params_ref(model._native_params())
+        tail = (ctx.drop, ctx.seed_t.data_ptr() if ctx.seed_t is not None else None, ctx.saved_buf.data_ptr(),
+                ctx.saved_buf.numel(), native.ptr(dout, "dout"))
+        tail2 = (dobs.data_ptr() if need_dx else None, ws.data_ptr(), ws.numel(), *ctx.tf, native.stream_handle(dev),
+                 ctx.flags)
+        if direct:  # one (+=) chain into the parameters' .grad
+            g = getattr(arena, "model_grads", None)
+            if g is None:
+                g = arena.model_grads = model._native_grads(arena)
+            code = L.dstd_model_rollout_tf_bwd(pref, n, tin, ctx.horizon, *tail, native.ext.model_grads_ref(g), *tail2)
+            native.check(code, "dstd_model_rollout_tf_bwd")
+        else:  # an arena per window, summed in backward order (_RolloutTrain.backward says why)
+            numel = native.arena_numel(ctx.params)
+            bufs = torch.zeros(windows, numel, dtype=torch.float32, device=dev)
+            for k in range(windows - 1, -1, -1):
+                g = model._native_grads(native.GradArena(ctx.params, dev, buf=bufs[k]))
+                code = L.dstd_model_rollout_tf_bwd_window(pref, n, tin, ctx.horizon, k, *tail,
+                                                          native.ext.model_grads_ref(g), *tail2)
+                native.check(code, "dstd_model_rollout_tf_bwd_window")
+            total = bufs[windows - 1]
+            for k in range(windows - 2, -1, -1):
+                total += bufs[k]
+            arena = native.GradArena(ctx.params, dev, buf=total)
+        ctx.saved_buf = ctx.seed_t = ctx.mask = ctx.tf = None
+        head = (None, None, None, dobs, None, None, None)  # model, paired, horizon, obs, teacher, mask, maps
+        if direct:
+            return (*head, *([None] * (1 if ctx.anchored else len(arena.params))))
+        if ctx.anchored:
+            for p, gv in zip(arena.params, arena.views()):
+                if gv is not None and p.requires_grad:
+                    if p.grad is None:
+                        p.grad = gv.clone()
+                    else:
+                        p.grad.add_(gv)
+            return (*head, None)
+        return (*head, *arena.views())
+
+
+class _RolloutTeacherPair(torch.autograd.Function):
+    """_RolloutTrainPair over _RolloutTeacher."""
+
+    @staticmethod
+    def forward(ctx, model, n, horizon, obs, teacher, mask, maps, *params):
+        out = _RolloutTeacher.forward(ctx, model, True, horizon, obs, teacher, mask, maps, *params)
+        ctx.half = n
+        return out[:n], out[n:]
+
+    @staticmethod
+    def backward(ctx, d1, d2):
+        n2, tin, v, c = ctx.shape
+        n = ctx.half
+        ref = d1 if d1 is not None else d2
+        if d1 is None:
+            d1 = ref.new_zeros((n, ctx.horizon, v, c))
+        if d2 is None:
+            d2 = ref.new_zeros((n2 - n, ctx.horizon, v, c))
+        return _RolloutTeacher.backward(ctx, torch.cat([d1, d2]))
+
+
 class BatchNorm(nn.Module):
     """BN1d over C*V channels of an NCTV tensor (reference :35-50).  Glue only:
     on the hot path every BatchNorm is folded into a kernel epilogue."""
@@ -1325,7 +1446,38 @@ class DSTDGCN(_NativeModule):
         native.lib()
         native.require_device(observed, "observed")
 
-    def rollout(self, observed, horizon=None):
+    def _teacher_args(self, teacher, teacher_mask, observed, halves, horizon, what):
+        """(teacher, mask as uint8) of a rollout call with scheduled sampling,
+        checked before anything runs: ``teacher`` [N, >= input_n + horizon, V, 3]
+        float32 and ``teacher_mask`` [windows, halves * N] bool or uint8, both
+        on the device of ``observed`` [N, input_n, V, 3]."""
+        if (teacher is None) != (teacher_mask is None):
+            raise ValueError(f"DSTDGCN.{what}: teacher and teacher_mask come together "
+                             f"(got {'teacher' if teacher_mask is None else 'teacher_mask'} alone)")
+        n, tin, v, c = observed.shape
+        windows = -(-horizon // self.output_time_frame)
+        for name, x in (("teacher", teacher), ("teacher_mask", teacher_mask)):
+            if not torch.is_tensor(x):
+                raise ValueError(f"DSTDGCN.{what}: {name} must be a tensor, got {type(x).__name__}")
+            if x.device != observed.device:
+                raise ValueError(f"DSTDGCN.{what}: {name} is on {x.device}, observed on {observed.device}")
+        if teacher.dtype != torch.float32:
+            raise ValueError(f"DSTDGCN.{what}: teacher must be float32, got {teacher.dtype}")
+        if teacher.dim() != 4 or teacher.shape[0] != n or tuple(teacher.shape[2:]) != (v, c):
+            raise ValueError(f"DSTDGCN.{what}: expected teacher [{n}, >= {tin + horizon}, {v}, {c}], "
+                             f"got {list(teacher.shape)}")
+        if teacher.shape[1] < tin + horizon:
+            raise ValueError(f"DSTDGCN.{what}: horizon {horizon} after {tin} observed frames needs a teacher of "
+                             f"{tin + horizon} frames, got {teacher.shape[1]}")
+        if teacher_mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"DSTDGCN.{what}: teacher_mask must be bool or uint8, got {teacher_mask.dtype}")
+        if tuple(teacher_mask.shape) != (windows, halves * n):
+            raise ValueError(f"DSTDGCN.{what}: expected teacher_mask [{windows}, {halves * n}], "
+                             f"got {list(teacher_mask.shape)}")
+        mask = teacher_mask.contiguous()
+        return teacher.detach().contiguous(), mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+    def rollout(self, observed, horizon=None, teacher=None, teacher_mask=None):
         """``predict`` that autograd can differentiate and a train-mode model
         can run: the ``horizon`` frames (default ``output_time_frame``) after
         ``observed`` [N, input_time_frame, V, 3], as [N, horizon, V, 3].
@@ -1343,25 +1495,58 @@ class DSTDGCN(_NativeModule):
         gradients bit for bit (tests/test_gpu_rollout.py) -- without K
         Functions of ~300 inputs each, and with the gradient of the window
         shuffling summed in a fixed order.  Eager only; no cross-rank
-        BatchNorm."""
+        BatchNorm.
+
+        Scheduled sampling: with ``teacher`` [N, >= input_time_frame + horizon,
+        V, 3] (each sample's own frames from the first observed one) and
+        ``teacher_mask`` [windows, N] (bool or uint8, on the device), sample b's
+        window k is built from the teacher's frames instead of what is known
+        so far wherever ``teacher_mask[k, b]`` is set, and no gradient crosses
+        that boundary (include/ext/dstd_gcn_teacher.h; row 0 is not read).  The
+        result is always the model's prediction.  Neither gets a gradient."""
         (n, tin, v, c), horizon = self._rollout_args(observed, horizon, "rollout")
         params = self._tree.get(self)[0]
+        tf = teacher is not None or teacher_mask is not None
+        if tf:
+            teacher, mask = self._teacher_args(teacher, teacher_mask, observed, 1, horizon, "rollout")
         if not self.training and not _needs_grad(observed, *params):
+            if tf:
+                raise RuntimeError("DSTDGCN.rollout: a teacher needs train mode or something to differentiate "
+                                   "(predict has no teacher)")
             return self.predict(observed, horizon)
         self._rollout_refusals(observed, "rollout")
         observed = observed.contiguous()
         if n == 0:  # empty batch: empty output
             return _mark(observed.new_empty(0, horizon, v, c), observed, *params)
+        if tf:
+            return _RolloutTeacher.apply(self, False, horizon, observed, teacher, mask, [(0, 1)],
+                                         *_anchor_of(self, observed, params))
         return _RolloutTrain.apply(self, False, horizon, observed, *_anchor_of(self, observed, params))
 
-    def rollout_pair(self, obs1, obs2, horizon=None):
+    def rollout_pair(self, obs1, obs2, horizon=None, teacher=None, teacher_mask=None):
         """``(self.rollout(obs1, horizon), self.rollout(obs2, horizon))`` as one
         chain over the concatenated batch, as ``forward_pair`` is for one
         window: in train mode every window keeps each half's own batch
         statistics and the running statistics take obs1's update then obs2's
         (DSTD_TRAIN_PAIRED), window by window.  Elsewhere (eval, shapes that
-        differ, an empty batch) it is the two calls."""
+        differ, an empty batch) it is the two calls.
+
+        Scheduled sampling: one ``teacher`` [N, Ttot, V, 3] serves both halves,
+        obs1's forwards in time and obs2's backwards from its last frame (the
+        time reversal of PredictionEngine.train: frame maps (0, +1) and
+        (Ttot - 1, -1)); ``teacher_mask`` is [windows, 2 N], obs1's samples
+        first."""
+        tf = teacher is not None or teacher_mask is not None
+        if tf:
+            if obs1.shape != obs2.shape or obs1.device != obs2.device:
+                raise ValueError("DSTDGCN.rollout_pair: one teacher serves two batches of one shape on one device, got "
+                                 f"{list(obs1.shape)} on {obs1.device} and {list(obs2.shape)} on {obs2.device}")
+            (n, tin, v, c), horizon = self._rollout_args(obs1, horizon, "rollout_pair")
+            teacher, mask = self._teacher_args(teacher, teacher_mask, obs1, 2, horizon, "rollout_pair")
         if not self.training or obs1.shape != obs2.shape or obs1.shape[0] == 0 or obs1.device != obs2.device:
+            if tf:  # the second call reads the teacher backwards as a tensor of its own
+                return (self.rollout(obs1, horizon, teacher, mask[:, :n]),
+                        self.rollout(obs2, horizon, teacher.flip(1), mask[:, n:]))
             return self.rollout(obs1, horizon), self.rollout(obs2, horizon)
         (n, tin, v, c), horizon = self._rollout_args(obs1, horizon, "rollout_pair")
         self._rollout_refusals(obs1, "rollout_pair")
@@ -1369,6 +1554,9 @@ class DSTDGCN(_NativeModule):
             raise RuntimeError("DSTDGCN.rollout_pair: eager only (tensor subclasses cannot be traced through the chain)")
         obs = torch.cat([obs1, obs2]).contiguous()
         params = self._tree.get(self)[0]
+        if tf:
+            return _RolloutTeacherPair.apply(self, n, horizon, obs, teacher, mask, [(0, 1), (teacher.shape[1] - 1, -1)],
+                                             *_anchor_of(self, obs, params))
         return _RolloutTrainPair.apply(self, n, horizon, obs, *_anchor_of(self, obs, params))
 
     def forward_pair(self, x1, x2):
