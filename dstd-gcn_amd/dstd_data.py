@@ -12,6 +12,10 @@ per batch: no DataLoader, no worker processes, no host-to-device copy and no
 host synchronisation per step.  ``PredictionEngine.train`` / ``test`` take the
 loader as they take the reference's.
 
+A set may carry a group per window (an action of a test set: ``groups``,
+``from_datasets``); ``PredictionEngine.test_groups`` then evaluates every group
+in one pass over one loader (include/ext/dstd_gcn_eval.h).
+
 There is no CPU gather: a set built with ``device="cpu"`` serves the host-side
 bookkeeping (weights, window starts, index order) only.
 """
@@ -114,6 +118,41 @@ class MeanStd:
         return data * s + m
 
 
+def group_table(groups, n_windows, mirrored=False, group_names=None):
+    """(table, names) of a grouped set: ``groups`` holds one non-negative int
+    per stored window; the table has one int32 entry per window index, so with
+    on-the-fly mirroring the half of the mirrored windows is appended (window
+    w + N has the group of w).  ``names``: one string per group 0 ..
+    max(groups), ``str(g)`` by default."""
+    g = np.asarray(groups)
+    if g.ndim != 1 or len(g) != n_windows or g.dtype.kind not in "iu":
+        raise ValueError(f"groups: one int per stored window ({n_windows}), got {g.dtype} {g.shape}")
+    if g.min() < 0 or g.max() >= 2 ** 31 - 1:
+        raise ValueError("groups: non-negative ints")
+    n_groups = int(g.max()) + 1
+    if group_names is None:
+        names = [str(k) for k in range(n_groups)]
+    else:
+        names = list(group_names)
+        if len(names) != n_groups or not all(isinstance(n, str) for n in names) or len(set(names)) != n_groups:
+            raise ValueError(f"group_names: {n_groups} distinct strings (one per group 0..{n_groups - 1}), "
+                             f"got {names!r}")
+    g = g.astype(np.int32)
+    return (np.concatenate((g, g)) if mirrored else g), names
+
+
+def _same_statistics(a, b):
+    """Two scale transforms carry the same statistics (MeanStdNorm-like: _mean, _std)."""
+    if a is b:
+        return True
+    if a is None or b is None:
+        return False
+    try:
+        return all(np.array_equal(np.asarray(getattr(a, n)), np.asarray(getattr(b, n))) for n in ("_mean", "_std"))
+    except AttributeError:
+        return False
+
+
 def _as_scaler(scaler):
     if scaler is None or (hasattr(scaler, "transform") and hasattr(scaler, "inverse")):
         return scaler
@@ -124,14 +163,21 @@ def _as_scaler(scaler):
 class DeviceSequences:
     """A dataset resident on the device: frames [F][D], windows as start rows.
 
-    Build with ``from_windows``, ``from_sequences`` or ``from_dataset``.  The
-    reference dataset objects' attributes a runner reads are here:
-    ``joint_weight_use`` / ``joint_weight_all``, ``dim_used``, ``time_tsfm``
-    (None), ``scale_tsfm``; plus ``nbytes`` (device memory held) and ``len``
-    (windows, the mirrored ones included)."""
+    Build with ``from_windows``, ``from_sequences``, ``from_dataset`` or
+    ``from_datasets``.  The reference dataset objects' attributes a runner
+    reads are here: ``joint_weight_use`` / ``joint_weight_all``, ``dim_used``,
+    ``time_tsfm`` (None), ``scale_tsfm``; plus ``nbytes`` (device memory held)
+    and ``len`` (windows, the mirrored ones included).
+
+    ``groups`` (one non-negative int per stored window; an action of a test
+    set) makes the set a grouped one for ``PredictionEngine.test_groups``:
+    ``groups`` is then the device int32 table with one entry per window index
+    (a mirrored window w + N has the group of w), ``group_names`` one string
+    per group (``str(g)`` by default) and ``n_groups`` their number.  Without
+    it ``groups`` is None and the set counts as one group named "all"."""
 
     def __init__(self, frames, starts, seq_len, dim_used, input_n, output_n, padding, device, mirror_src=None,
-                 scale_tsfm=None, joint_weights=None):
+                 scale_tsfm=None, joint_weights=None, groups=None, group_names=None):
         frames = np.asarray(frames, dtype=np.float64)
         starts = np.asarray(starts, dtype=np.int64)
         if frames.ndim != 2 or frames.shape[0] < 1 or frames.shape[1] % 3 != 0:
@@ -169,6 +215,14 @@ class DeviceSequences:
         self._dim_used = torch.from_numpy(dim_used.astype(np.int32)).to(dev)
         self._frame_in, self._frame_inv = torch.from_numpy(fwd).to(dev), torch.from_numpy(inv).to(dev)
         self._mirror_src = torch.from_numpy(mirror_src).to(dev) if mirror_src is not None else None
+        if groups is None:
+            if group_names is not None:
+                raise ValueError("group_names without groups")
+            self.groups, self.group_names = None, ["all"]
+        else:
+            table, self.group_names = group_table(groups, self.n_windows, mirror_src is not None, group_names)
+            self.groups = torch.from_numpy(table).to(dev)
+        self.n_groups = len(self.group_names)
         self._store = native.SeqStore(
             frames=self._frames.data_ptr(), used=self._used.data_ptr() if self._used is not None else None,
             starts=self._starts.data_ptr(), F=F, N=self.n_windows, T=T, D=D, Du=len(dim_used),
@@ -179,12 +233,13 @@ class DeviceSequences:
     # ---- constructors ---------------------------------------------------------------
     @classmethod
     def from_windows(cls, all_seqs, dim_used, input_n, output_n, padding=True, device="cuda", mirror=None,
-                     scaler=None):
+                     scaler=None, groups=None, group_names=None):
         """Materialised windows [N][T][D] (what load_data_3d returns), stored
         back to back.  mirror=(left, right) joint lists doubles the set as
         get_mirror does; scaler: a MeanStdNorm-like object, (mean, std), or
         True for the statistics of the used columns over every window frame
-        (dataset/h36m.py:81-85)."""
+        (dataset/h36m.py:81-85).  groups: one int per window of all_seqs (a
+        mirrored window inherits its group)."""
         w = np.asarray(all_seqs, dtype=np.float64)
         if w.ndim != 3 or w.shape[2] % 3 != 0 or w.shape[1] < 2:
             raise ValueError(f"all_seqs: expected [N][T >= 2][D], D a multiple of 3, got {w.shape}")
@@ -192,22 +247,27 @@ class DeviceSequences:
         mirror_src = mirror_source(w.shape[2] // 3, *mirror) if mirror is not None else None
         full = w if mirror_src is None else np.concatenate((w, mirror_frames(w, mirror_src)), axis=0)
         weights = window_joint_weights(full, dim_used)
+        if groups is not None and len(np.asarray(groups)) != w.shape[0]:
+            raise ValueError(f"groups: one int per window ({w.shape[0]}), got {len(np.asarray(groups))}")
         if scaler is not None:  # mirror, then statistics, then scale -- on stored mirrored frames
+            if groups is not None and mirror_src is not None:
+                groups = np.concatenate((np.asarray(groups), np.asarray(groups)))
             w, mirror_src = full, None
             if scaler is True:
                 u = w[:, :, np.asarray(dim_used)].reshape(w.shape[0] * w.shape[1], -1)
                 scaler = (np.mean(u, axis=0), np.std(u, axis=0))
         n, t, d = w.shape
         return cls(w.reshape(n * t, d), np.arange(n, dtype=np.int64) * t, t, dim_used, input_n, output_n, padding,
-                   device, mirror_src, _as_scaler(scaler), weights)
+                   device, mirror_src, _as_scaler(scaler), weights, groups, group_names)
 
     @classmethod
     def from_sequences(cls, sequences, seq_len, dim_used, input_n, output_n, padding=True, device="cuda",
-                       mirror=None, scaler=None):
+                       mirror=None, scaler=None, groups=None, group_names=None):
         """Whole sequences [F_i][D]: every start 0..F_i - seq_len of every
         sequence is a window (the training selection of load_data_3d,
         dataset/utils.py:860-866), frames stored once.  The joint weights come
-        from how many windows hold each pair of consecutive frames."""
+        from how many windows hold each pair of consecutive frames.  groups:
+        one int per sequence, which every window of the sequence inherits."""
         seqs = [np.asarray(s, dtype=np.float64) for s in sequences]
         T = int(seq_len)
         if not seqs or any(s.ndim != 2 or s.shape[1] != seqs[0].shape[1] or s.shape[0] < T for s in seqs) or T < 2:
@@ -219,10 +279,17 @@ class DeviceSequences:
         mirror_src = mirror_source(D // 3, *mirror) if mirror is not None else None
         if scaler is True:
             raise ValueError("from_sequences takes the scaler's statistics from the caller")
+        if groups is not None:
+            groups = np.asarray(groups)
+            if groups.ndim != 1 or len(groups) != len(seqs):
+                raise ValueError(f"groups: one int per sequence ({len(seqs)}), got shape {groups.shape}")
         if scaler is not None and mirror_src is not None:
             seqs = seqs + [mirror_frames(s, mirror_src) for s in seqs]
+            groups = np.concatenate((groups, groups)) if groups is not None else None
         offsets = np.concatenate([[0], np.cumsum([len(s) for s in seqs])])
         starts = np.concatenate([off + np.arange(len(s) - T + 1) for off, s in zip(offsets, seqs)])
+        if groups is not None:
+            groups = np.repeat(groups, [len(s) - T + 1 for s in seqs])
         # mean |x[t+1] - x[t]| over every window: pair p of a sequence lies in
         # windows max(0, p - T + 2) .. min(p, F_i - T)
         motion = np.zeros(D // 3)
@@ -236,7 +303,7 @@ class DeviceSequences:
         if scaler is not None:
             mirror_src = None
         return cls(np.concatenate(seqs, axis=0), starts, T, dim_used, input_n, output_n, padding, device, mirror_src,
-                   _as_scaler(scaler), _normalised_weights(motion, dim_used))
+                   _as_scaler(scaler), _normalised_weights(motion, dim_used), groups, group_names)
 
     @classmethod
     def from_dataset(cls, ds, input_n, output_n, padding=True, device="cuda"):
@@ -248,6 +315,38 @@ class DeviceSequences:
         return cls(w.reshape(n * t, d), np.arange(n, dtype=np.int64) * t, t, ds.dim_used, input_n, output_n, padding,
                    device, None, getattr(ds, "scale_tsfm", None), (ds.joint_weight_all, ds.joint_weight_use))
 
+    @classmethod
+    def from_datasets(cls, datasets, input_n, output_n, padding=True, device="cuda"):
+        """An ordered mapping {name: reference dataset object} (the runners'
+        per-action test sets, one Human36M / CMUMocap per action) as one
+        grouped set: their all_seqs back to back in mapping order, one group
+        per entry.  dim_used, window length and D must agree; the scale_tsfm
+        is the first entry's, and the others must carry the same statistics.
+        A test set: no joint weights."""
+        items = list(datasets.items())
+        if not items:
+            raise ValueError("from_datasets: no dataset")
+        names = [str(k) for k, _ in items]
+        first = items[0][1]
+        dim_used = np.asarray(first.dim_used)
+        scale = getattr(first, "scale_tsfm", None)
+        windows, groups = [], []
+        for g, (name, ds) in enumerate(items):
+            w = np.asarray(ds.all_seqs, dtype=np.float64)
+            if w.ndim != 3 or (windows and w.shape[1:] != windows[0].shape[1:]):
+                raise ValueError(f"from_datasets: all_seqs of '{name}' is {w.shape}, "
+                                 f"'{names[0]}' has windows of {windows[0].shape[1:] if windows else '[T][D]'}")
+            if not np.array_equal(np.asarray(ds.dim_used), dim_used):
+                raise ValueError(f"from_datasets: dim_used of '{name}' differs from that of '{names[0]}'")
+            if not _same_statistics(scale, getattr(ds, "scale_tsfm", None)):
+                raise ValueError(f"from_datasets: scale_tsfm of '{name}' differs from that of '{names[0]}'")
+            windows.append(w)
+            groups.append(np.full(len(w), g, dtype=np.int64))
+        w = np.concatenate(windows, axis=0)
+        n, t, d = w.shape
+        return cls(w.reshape(n * t, d), np.arange(n, dtype=np.int64) * t, t, dim_used, input_n, output_n, padding,
+                   device, None, scale, None, np.concatenate(groups), names)
+
     # ---- the set --------------------------------------------------------------------
     def __len__(self):
         return self.n_windows * (2 if self._mirror_src is not None else 1)
@@ -256,7 +355,7 @@ class DeviceSequences:
     def nbytes(self):
         """Device memory the set holds."""
         held = (self._frames, self._used, self._starts, self._dim_used, self._frame_in, self._frame_inv,
-                self._mirror_src)
+                self._mirror_src, self.groups)
         return sum(t.numel() * t.element_size() for t in held if t is not None)
 
     @property
@@ -336,4 +435,4 @@ class DeviceLoader:
             yield self.seqs.gather(idx)
 
 
-__all__ = ["DeviceSequences", "DeviceLoader", "MeanStd", "frame_maps", "mirror_source"]
+__all__ = ["DeviceSequences", "DeviceLoader", "MeanStd", "frame_maps", "group_table", "mirror_source"]

@@ -24,6 +24,11 @@ format as the reference, driving the MI355X model:
   DistributedSampler) and the per-frame sums and sample counts are
   all-reduced (dstd_dist.reduce_partials), so every rank returns the metric of
   the whole loader.
+* ``test_groups``: the protocol's per-action table from one pass over a
+  resident test set whose windows carry a group (dstd_data.DeviceSequences
+  ``groups``): batches mix groups, the metric reads the targets from the
+  resident frames (dstd_store_group_mpjpe, include/ext/dstd_gcn_eval.h) into
+  sums[group][frame] on the device, one synchronisation for the whole table.
 * ``save`` / ``recover`` (:159-182): the same ``{"lr", "err", "model",
   "optimizer", "scheduler", "epoch"}`` dict with ``model.``-prefixed keys;
   recover loads with ``weights_only=True``.
@@ -97,6 +102,27 @@ def _world():
     if dist.is_available() and dist.is_initialized():
         return dist.get_rank(), dist.get_world_size()
     return 0, 1
+
+
+def combine_groups(sums, counts):
+    """The protocol's table from accumulated sums [G][K] and counts [G]
+    (runner/h36m.py:106-135): (avg, t_metric, {g: (avg_g, metric_g)}) with
+    metric_g = sums[g] / counts[g] of every non-empty group g, in group order,
+    t_metric their unweighted mean and avg = t_metric.mean() (the mean of the
+    avg_g).  An empty group is left out of the table and of the means."""
+    sums = np.asarray(sums, dtype=np.float64)
+    counts = np.asarray(counts)
+    if sums.ndim != 2 or counts.shape != (sums.shape[0],) or sums.shape[1] < 1:
+        raise ValueError(f"combine_groups: sums [G][K] and counts [G], got {sums.shape} and {counts.shape}")
+    table = {}
+    for g in range(len(counts)):
+        if counts[g] > 0:
+            m = sums[g] / float(counts[g])
+            table[g] = (float(m.mean()), m)
+    if not table:
+        raise ValueError("combine_groups: every group is empty")
+    t_metric = np.mean([m for _, m in table.values()], axis=0)
+    return float(t_metric.mean()), t_metric, table
 
 
 def _to_dev(x, dev):
@@ -496,6 +522,82 @@ class PredictionEngine:
         # t_l.avg of the reference = sum over (batch, frame) of metric_k / (N * frames)
         return float(t_metric.mean()), t_metric
 
+    def test_groups(self, loader, input_n=10, eval_frame=None, joint_to_ignore=None, joint_equal=None,
+                    scale_tsfm=None, horizon=None):
+        """The protocol's whole table in one pass over a resident test set
+        whose windows carry a group (an action; dstd_data.DeviceSequences
+        ``groups``): what the runners build by one ``test`` per action
+        (runner/h36m.py:106-135).  Returns ``(avg, t_metric, table)``:
+        ``table`` is ``{group name: (avg_g, per-frame metric_g)}`` in group
+        order, empty groups left out; ``t_metric`` the unweighted mean of the
+        metric_g over the non-empty groups and ``avg = t_metric.mean()``.
+
+        ``loader`` is a DeviceLoader; its batches may mix groups at any batch
+        size.  Only ``inputs`` is gathered: the metric reads the targets from
+        the resident frames (dstd_store_group_mpjpe, one launch per batch into
+        sums[group][frame] and counts[group] on the device), and the host
+        synchronises once, at the end.  The model runs exactly as in ``test``,
+        ``horizon`` included; ``dim_used`` is the set's.  A set without groups
+        is one group named "all"."""
+        from dstd_data import DeviceLoader
+        if not isinstance(loader, DeviceLoader):
+            raise TypeError(f"test_groups: loader must be a dstd_data.DeviceLoader, got {type(loader).__name__}")
+        assert eval_frame is not None
+        if _world()[1] > 1:
+            raise NotImplementedError("test_groups: a resident set is not sharded over ranks; "
+                                      "evaluate on one rank or use test")
+        seqs = loader.seqs
+        if getattr(seqs, "time_tsfm", None) is not None:
+            raise ValueError("test_groups: a resident set carries no time transform; time_tsfm must be None")
+        seq_len, D = seqs.seq_len, seqs.n_dims
+        if horizon is not None and seq_len != input_n + horizon:
+            raise ValueError(f"test_groups: horizon {horizon} after {input_n} observed frames needs windows of "
+                             f"{input_n + horizon} frames, got {seq_len}")
+        for f in eval_frame:
+            if not 0 <= input_n + int(f) < seq_len:
+                raise ValueError(f"eval frame {input_n + int(f)} outside the {seq_len}-frame sequence")
+        dev = self.device
+        G, K = seqs.n_groups, len(eval_frame)
+        sums = torch.zeros(G, K, dtype=torch.float32, device=dev)
+        counts = torch.zeros(G, dtype=torch.int32, device=dev)
+        group_ptr = seqs.groups.data_ptr() if seqs.groups is not None else None
+        store = native.ext_eval.seq_store_ref(seqs._store)
+        index_cache = {}
+        self.model.eval()
+        with torch.no_grad():
+            for idx in loader.index_batches():
+                inputs = seqs.gather(idx, outputs=("inputs",))[0]
+                if horizon is not None:
+                    observed = self.transform(inputs)[:, :input_n].contiguous()
+                    outputs = self.inverse(self.model.model.predict(observed, horizon))
+                else:
+                    outputs = self.inverse(self.model(self.transform(inputs), False))
+                if isinstance(outputs, list):
+                    outputs = outputs[0]
+                    n, t = outputs.shape[:2]
+                    outputs = outputs.view(n, t, -1)
+                if scale_tsfm is not None:
+                    outputs = scale_tsfm.inverse(outputs)
+                outputs = outputs.contiguous()
+                t_out0 = input_n if outputs.shape[1] != seq_len else 0
+                if outputs.shape[1] != seq_len - t_out0:
+                    raise ValueError(f"test_groups: outputs of {outputs.shape[1]} frames for windows of {seq_len}")
+                if t_out0 not in index_cache:
+                    index_cache[t_out0] = self._metric_indices(D, outputs.shape[2], seq_len, input_n, eval_frame,
+                                                               seqs.dim_used, joint_to_ignore, joint_equal)
+                used_pos, joint_src, frames = index_cache[t_out0]
+                code = native.lib().dstd_store_group_mpjpe(
+                    store, idx.data_ptr(), idx.numel(), native.ptr(outputs, "outputs"), t_out0, used_pos.data_ptr(),
+                    outputs.shape[2], joint_src.data_ptr(), frames.data_ptr(), K, group_ptr, G, sums.data_ptr(),
+                    counts.data_ptr(), native.stream_handle(outputs.device))
+                native.check(code, "dstd_store_group_mpjpe")
+            both = torch.cat((sums.double().view(-1), counts.double())).cpu().numpy()  # the one synchronisation
+        avg, t_metric, by_group = combine_groups(both[:G * K].reshape(G, K), both[G * K:].astype(np.int64))
+        table = {seqs.group_names[g]: v for g, v in by_group.items()}
+        for name, (avg_g, _) in table.items():
+            self.logger.info(f"action: {name}|test|loss:{avg_g:.2f}")
+        return avg, t_metric, table
+
     def _rollout(self, inputs, all_seqs, input_n, horizon):
         """test(horizon=...): the model's ``predict`` on the observed frames of
         one batch, in the engine's [n, horizon, dims] form."""
@@ -589,4 +691,4 @@ class PredictionEngine:
         return pred[:, :, src].view(n, T, J, 3)
 
 
-__all__ = ["ModelWrapper", "PredictionEngine", "AccumLoss"]
+__all__ = ["ModelWrapper", "PredictionEngine", "AccumLoss", "combine_groups"]
