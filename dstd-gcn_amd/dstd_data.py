@@ -16,6 +16,12 @@ A set may carry a group per window (an action of a test set: ``groups``,
 ``from_datasets``); ``PredictionEngine.test_groups`` then evaluates every group
 in one pass over one loader (include/ext/dstd_gcn_eval.h).
 
+``Augment`` describes continuous augmentations -- a per-sample rotation, scale
+and shift of every joint, uniform noise on the observed frames -- that the
+gather applies in its one launch (include/ext/dstd_gcn_augment.h):
+``DeviceLoader(..., augment=Augment(...))``, or ``gather(index, transform=,
+noise=, noise_seed=)`` for a caller's own transforms.
+
 There is no CPU gather: a set built with ``device="cpu"`` serves the host-side
 bookkeeping (weights, window starts, index order) only.
 """
@@ -158,6 +164,122 @@ def _as_scaler(scaler):
         return scaler
     mean, std = scaler
     return MeanStd(mean, std)
+
+
+_FP32_MAX = float(np.finfo(np.float32).max)
+
+
+def _check_augmentation(seqs, index, transform, noise, noise_seed):
+    """The augmentation arguments of DeviceSequences.gather, checked before
+    anything else (no device needed): (noise as a float, noise_seed mod 2^64)."""
+    try:
+        noise = float(noise)
+    except (TypeError, ValueError):
+        raise ValueError(f"noise: a non-negative finite amplitude, got {noise!r}") from None
+    if not 0.0 <= noise <= _FP32_MAX:  # NaN fails both comparisons
+        raise ValueError(f"noise: a non-negative finite (fp32) amplitude, got {noise!r}")
+    if transform is not None:
+        if seqs.scale_tsfm is not None or seqs._used is not None:
+            raise ValueError("transform: a scaled set holds standardised coordinates, which a rigid transform "
+                             "does not apply to (noise alone is allowed)")
+        B = index.numel()
+        if (not isinstance(transform, torch.Tensor) or transform.dtype != torch.float32
+                or tuple(transform.shape) not in ((B, 12), (B, 3, 4)) or not transform.is_contiguous()
+                or transform.device != seqs._frames.device):
+            raise ValueError(f"transform: a contiguous float32 [{B}, 12] or [{B}, 3, 4] tensor on "
+                             f"{seqs._frames.device}, got {_describe(transform)}")
+    return noise, int(noise_seed) % 2 ** 64
+
+
+def _describe(t):
+    if not isinstance(t, torch.Tensor):
+        return type(t).__name__
+    return f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else ", not contiguous")
+
+
+class Augment:
+    """Continuous augmentations of a batch, applied inside the gather: a
+    per-sample affine transform ``[A | t]`` of every joint, ``A = scale * R``,
+    and a uniform jitter of the observed frames (``inputs`` / ``inputs_inv``).
+
+    ``rotate``: ``(axis, max_angle)`` -- an angle uniform in ``[-max_angle,
+    max_angle]`` (radians) about coordinate axis 0, 1 or 2; there is no
+    default axis, the caller names the vertical of their data -- or ``"so3"``,
+    a uniformly distributed rotation.  ``scale``: ``(lo, hi)``, uniform, ``0 <
+    lo <= hi``.  ``shift``: an amplitude; each component of ``t`` is uniform in
+    ``[-shift, shift]``.  ``noise``: the jitter's amplitude (not drawn here:
+    the gather derives it from a seed, the window and the frame)."""
+
+    def __init__(self, rotate=None, scale=None, shift=None, noise=0.0):
+        if rotate is not None and rotate != "so3":
+            try:
+                axis, max_angle = rotate
+                ok = axis in (0, 1, 2) and not isinstance(axis, bool) and 0.0 <= float(max_angle) < float("inf")
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f'rotate: (axis 0 / 1 / 2, max_angle >= 0) or "so3", got {rotate!r}')
+            rotate = (int(axis), float(max_angle))
+        if scale is not None:
+            try:
+                lo, hi = (float(v) for v in scale)
+                ok = 0.0 < lo <= hi < float("inf")
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"scale: (lo, hi) with 0 < lo <= hi, got {scale!r}")
+            scale = (lo, hi)
+        if shift is not None:
+            shift = float(shift)
+            if not 0.0 <= shift < float("inf"):
+                raise ValueError(f"shift: a non-negative finite amplitude, got {shift!r}")
+        noise = float(noise)
+        if not 0.0 <= noise <= _FP32_MAX:
+            raise ValueError(f"noise: a non-negative finite (fp32) amplitude, got {noise!r}")
+        self.rotate, self.scale, self.shift, self.noise = rotate, scale, shift, noise
+
+    def draw(self, B, generator, device):
+        """One ``[A | t]`` per sample: fp32 ``[B, 12]`` on ``device``, or None
+        when neither rotate, scale nor shift is set.  Torch ops on ``device``
+        fed from ``generator`` (a generator of that device), in the fixed
+        order rotate, scale, shift; no host synchronisation."""
+        if self.rotate is None and self.scale is None and self.shift is None:
+            return None
+        dev = torch.device(device)
+
+        def rand(*shape):
+            return torch.rand(*shape, generator=generator, device=dev, dtype=torch.float32)
+
+        m = torch.zeros(B, 3, 4, dtype=torch.float32, device=dev)
+        one = torch.ones(B, dtype=torch.float32, device=dev)
+        if self.rotate == "so3":
+            # a unit quaternion from four normals is uniform on the 3-sphere;
+            # the homogeneous form of its matrix (|q|^2 on the diagonal, not 1)
+            # stays orthogonal to first order when |q| is a few ulp off 1
+            g = torch.randn(B, 4, generator=generator, device=dev, dtype=torch.float32)
+            w, x, y, z = (g / g.norm(dim=1, keepdim=True).clamp_min(1e-30)).unbind(1)
+            m[:, 0, 0] = (w * w + x * x) - (y * y + z * z)
+            m[:, 1, 1] = (w * w + y * y) - (x * x + z * z)
+            m[:, 2, 2] = (w * w + z * z) - (x * x + y * y)
+            m[:, 0, 1], m[:, 1, 0] = 2 * (x * y - w * z), 2 * (x * y + w * z)
+            m[:, 0, 2], m[:, 2, 0] = 2 * (x * z + w * y), 2 * (x * z - w * y)
+            m[:, 1, 2], m[:, 2, 1] = 2 * (y * z - w * x), 2 * (y * z + w * x)
+        elif self.rotate is not None:
+            axis, max_angle = self.rotate
+            i, j = (axis + 1) % 3, (axis + 2) % 3  # right-handed about `axis`
+            theta = (2 * rand(B) - 1) * max_angle
+            c, s = torch.cos(theta), torch.sin(theta)
+            m[:, i, i], m[:, i, j], m[:, j, i], m[:, j, j] = c, -s, s, c
+            m[:, axis, axis] = one  # the axis row and column: constants, never computed
+        else:
+            m[:, 0, 0] = m[:, 1, 1] = m[:, 2, 2] = one
+        if self.scale is not None:
+            lo, hi = self.scale
+            k = (lo + (hi - lo) * rand(B)).clamp_(lo, hi)
+            m[:, :, :3] *= k[:, None, None]  # 1 * k and 0 * k are exact
+        if self.shift is not None:
+            m[:, :, 3] = (2 * rand(B, 3) - 1) * self.shift
+        return m.view(B, 12)
 
 
 class DeviceSequences:
@@ -362,11 +484,21 @@ class DeviceSequences:
     def starts(self):
         return self._starts
 
-    def gather(self, index, outputs=("inputs", "inputs_inv", "targets", "all_seqs"), out=None):
+    def gather(self, index, outputs=("inputs", "inputs_inv", "targets", "all_seqs"), out=None, transform=None,
+               noise=0.0, noise_seed=0):
         """(inputs, inputs_inv, targets, all_seqs) of the windows ``index``
         (int64 device tensor [B]) by one dstd_batch_gather on the current
         stream; a name missing from ``outputs`` is not produced (None).
-        ``out``: tensors to write into instead of fresh ones, by name."""
+        ``out``: tensors to write into instead of fresh ones, by name.
+
+        ``transform`` (contiguous fp32 [B, 12] or [B, 3, 4] on the set's
+        device: a row-major 3x4 [A | t] per sample, applied to every joint of
+        all four tensors) and ``noise`` (amplitude of a uniform jitter of
+        ``inputs`` / ``inputs_inv`` alone, keyed by ``noise_seed``, the window
+        and the source frame) augment the batch in the same single launch
+        (dstd_batch_gather_aug, include/ext/dstd_gcn_augment.h).  A scaled set
+        takes noise, in the scaler's units, but no transform."""
+        noise, noise_seed = _check_augmentation(self, index, transform, noise, noise_seed)
         if self.device.type != "cuda":
             raise RuntimeError(f"DeviceSequences.gather runs on the MI355X only (the set is on {self.device}); "
                                "there is no CPU fallback")
@@ -384,10 +516,17 @@ class DeviceSequences:
                 raise ValueError(f"{n}: expected {shapes[n]}, got {tuple(t.shape)}")
             res[n] = t
         p = {n: native.ptr(t, n) for n, t in res.items()}
-        code = native.lib().dstd_batch_gather(ctypes.byref(self._store), index.data_ptr(), B, p.get("inputs"),
-                                              p.get("inputs_inv"), p.get("targets"), p.get("all_seqs"),
-                                              native.stream_handle(self._frames.device))
-        native.check(code, "dstd_batch_gather")
+        if transform is None and noise == 0.0:
+            code = native.lib().dstd_batch_gather(ctypes.byref(self._store), index.data_ptr(), B, p.get("inputs"),
+                                                  p.get("inputs_inv"), p.get("targets"), p.get("all_seqs"),
+                                                  native.stream_handle(self._frames.device))
+            native.check(code, "dstd_batch_gather")
+        else:
+            code = native.lib().dstd_batch_gather_aug(
+                native.ext_augment.seq_store_ref(self._store), index.data_ptr(), B,
+                transform.data_ptr() if transform is not None else None, noise, noise_seed, p.get("inputs"),
+                p.get("inputs_inv"), p.get("targets"), p.get("all_seqs"), native.stream_handle(self._frames.device))
+            native.check(code, "dstd_batch_gather_aug")
         return tuple(res.get(n) for n in ("inputs", "inputs_inv", "targets", "all_seqs"))
 
 
@@ -397,9 +536,16 @@ class DeviceLoader:
     one launch per batch and no host synchronisation.  Indices are generated
     on the set's device; ``shuffle`` draws a permutation per epoch from a
     device generator seeded ``seed + epoch`` (epochs counted per iteration
-    started).  ``last_index`` is the index tensor of the batch just yielded."""
+    started).  ``last_index`` is the index tensor of the batch just yielded.
 
-    def __init__(self, seqs, batch_size, shuffle=False, drop_last=False, seed=0):
+    ``augment`` (an ``Augment``) transforms and jitters every batch inside its
+    gather.  The transforms come from a generator of their own, seeded ``seed
+    + epoch`` when an epoch starts, so the order of windows is the same with
+    and without augmentation; batch ``i`` of an epoch uses the noise seed
+    ``noise_seed(seed, epoch, i)``.  ``last_transform`` and ``last_noise_seed``
+    describe the batch just yielded (None without ``augment``)."""
+
+    def __init__(self, seqs, batch_size, shuffle=False, drop_last=False, seed=0, augment=None):
         if batch_size < 1:
             raise ValueError(f"batch_size {batch_size}")
         self.seqs, self.batch_size = seqs, int(batch_size)
@@ -408,6 +554,11 @@ class DeviceLoader:
         self.last_index = None
         self._order = None
         self._generator = None
+        if augment is not None and not isinstance(augment, Augment):
+            raise TypeError(f"augment: an Augment or None, got {type(augment).__name__}")
+        self.augment = augment
+        self.last_transform = self.last_noise_seed = None
+        self._aug_generator = None
 
     def __len__(self):
         n = len(self.seqs)
@@ -429,10 +580,28 @@ class DeviceLoader:
         for i in range(len(self)):
             yield order[i * self.batch_size:(i + 1) * self.batch_size]
 
+    @staticmethod
+    def noise_seed(seed, epoch, i):
+        """The noise seed of batch ``i`` of epoch ``epoch`` (Python ints)."""
+        return (((int(seed) + int(epoch)) << 32) ^ int(i)) % 2 ** 64
+
     def __iter__(self):
-        for idx in self.index_batches():
+        aug = self.augment
+        if aug is None:
+            for idx in self.index_batches():
+                self.last_index = idx
+                yield self.seqs.gather(idx)
+            return
+        epoch, dev = self.epoch, self.seqs.device  # index_batches counts the epoch when its first batch is drawn
+        if self._aug_generator is None:
+            self._aug_generator = torch.Generator(device=dev)
+        self._aug_generator.manual_seed(self.seed + epoch)
+        for i, idx in enumerate(self.index_batches()):
             self.last_index = idx
-            yield self.seqs.gather(idx)
+            self.last_transform = aug.draw(idx.numel(), self._aug_generator, dev)
+            self.last_noise_seed = self.noise_seed(self.seed, epoch, i)
+            yield self.seqs.gather(idx, transform=self.last_transform, noise=aug.noise,
+                                   noise_seed=self.last_noise_seed)
 
 
-__all__ = ["DeviceSequences", "DeviceLoader", "MeanStd", "frame_maps", "group_table", "mirror_source"]
+__all__ = ["Augment", "DeviceSequences", "DeviceLoader", "MeanStd", "frame_maps", "group_table", "mirror_source"]

@@ -542,6 +542,9 @@ class PredictionEngine:
         from dstd_data import DeviceLoader
         if not isinstance(loader, DeviceLoader):
             raise TypeError(f"test_groups: loader must be a dstd_data.DeviceLoader, got {type(loader).__name__}")
+        if getattr(loader, "augment", None) is not None:
+            raise ValueError("test_groups: the metric reads its targets from the resident frames, which an "
+                             "augmenting loader does not transform; evaluate with a loader without augment")
         assert eval_frame is not None
         if _world()[1] > 1:
             raise NotImplementedError("test_groups: a resident set is not sharded over ranks; "
