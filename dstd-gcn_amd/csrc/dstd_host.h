@@ -63,4 +63,26 @@ inline bool block_ptrs_ok(const dstd_block_params* p) {
   return true;
 }
 
+// What the chains over dstd_model_fwd_ex (dstd_predict.hip,
+// dstd_predict_stride.hip) check before their first launch, as the forward
+// itself judges it.  The flags and the shape go through the schedule query
+// that shares the forward's checks (cus = 1: no device is asked).
+inline int fwd_shape_code(int B, int T, int V, int C, int layers, unsigned flags) {
+  const int n = dstd_model_fwd_schedule(B, T, V, C, layers, flags, 0, 0, 1, nullptr, 0);
+  return n < 0 ? n : DSTD_OK;
+}
+inline bool fwd_flags_ok(unsigned flags) { return fwd_shape_code(1, 2, 1, 1, 0, flags) == DSTD_OK; }
+
+// the parameter pointers dstd_model_fwd_ex checks (after the shape, before the workspace)
+inline bool model_ptrs_ok(const dstd_model_params* p) {
+  const int C = p->num_feature;
+  if (!block_ptrs_ok(&p->st_in) || !block_ptrs_ok(&p->st_out) || !bn_ok(p->bn_in) || !p->prelu) return false;
+  if (p->st_in.cin != 6 || p->st_in.cout != C || p->st_out.cin != C || p->st_out.cout != 3) return false;
+  for (int i = 0; i < p->num_layers; ++i) {
+    if (!block_ptrs_ok(&p->enc[i]) || !bn_ok(p->enc_bn[i]) || !p->enc_prelu[i]) return false;
+    if (p->enc[i].cin != C || p->enc[i].cout != C) return false;
+  }
+  return true;
+}
+
 }  // namespace dstd

@@ -11,30 +11,6 @@
 
 using namespace dstd;
 
-namespace {
-
-// The flags and the shape as dstd_model_fwd_ex judges them, through the
-// schedule query that shares its checks (cus = 1: no device is asked).
-int shape_code(int B, int T, int V, int C, int layers, unsigned flags) {
-  const int n = dstd_model_fwd_schedule(B, T, V, C, layers, flags, 0, 0, 1, nullptr, 0);
-  return n < 0 ? n : DSTD_OK;
-}
-bool flags_ok(unsigned flags) { return shape_code(1, 2, 1, 1, 0, flags) == DSTD_OK; }
-
-// the parameter pointers dstd_model_fwd_ex checks (after the shape, before the workspace)
-bool model_ptrs_ok(const dstd_model_params* p) {
-  const int C = p->num_feature;
-  if (!block_ptrs_ok(&p->st_in) || !block_ptrs_ok(&p->st_out) || !bn_ok(p->bn_in) || !p->prelu) return false;
-  if (p->st_in.cin != 6 || p->st_in.cout != C || p->st_out.cin != C || p->st_out.cout != 3) return false;
-  for (int i = 0; i < p->num_layers; ++i) {
-    if (!block_ptrs_ok(&p->enc[i]) || !bn_ok(p->enc_bn[i]) || !p->enc_prelu[i]) return false;
-    if (p->enc[i].cin != C || p->enc[i].cout != C) return false;
-  }
-  return true;
-}
-
-}  // namespace
-
 extern "C" {
 
 size_t dstd_model_predict_workspace_bytes(int B, int T, int V, int num_feature, int num_layers) {
@@ -49,11 +25,11 @@ int dstd_model_predict(const dstd_model_params* p, const float* obs, int B, int 
   const int T = p->T, V = p->V, C = p->num_feature, L_ = p->num_layers, Tin = input_n;
   if (Tin < 1 || Tin >= T || horizon < 1) return DSTD_EINVAL;
   const int Tout = T - Tin, K = (int)(((long long)horizon + Tout - 1) / Tout);
-  if (!flags_ok(flags)) return DSTD_EINVAL;
+  if (!fwd_flags_ok(flags)) return DSTD_EINVAL;
   // (2) envelope
   if (K > DSTD_PREDICT_MAX_WINDOWS) return DSTD_ELIMIT;
   if (p->in_channels != 6) return DSTD_EINVAL;
-  if (const int e = shape_code(B, T, V, C, L_, flags)) return e;
+  if (const int e = fwd_shape_code(B, T, V, C, L_, flags)) return e;
   if (!model_ptrs_ok(p)) return DSTD_EINVAL;
   // (3) workspace
   if (workspace_bytes < dstd_model_predict_workspace_bytes(B, T, V, C, L_)) return DSTD_EWORKSPACE;

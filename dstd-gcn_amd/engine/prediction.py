@@ -442,14 +442,17 @@ class PredictionEngine:
 
     # ------------------------------------------------------------------
     def test(self, test_loader, input_n=10, eval_frame=None, dim_used=None, joint_to_ignore=None, joint_equal=None,
-             time_tsfm=None, scale_tsfm=None, action=None, save_path=None, horizon=None):
+             time_tsfm=None, scale_tsfm=None, action=None, save_path=None, horizon=None, stride=None):
         """``horizon`` (None: the reference's path, one forward of the padded
         window): evaluate a rollout instead -- the first ``input_n`` frames of
         ``inputs`` are the observations, ``model.predict`` returns the
         ``horizon`` frames after them in one native call, and ``all_seqs`` must
         hold ``input_n + horizon`` frames; ``eval_frame`` may reach
-        ``horizon - 1``."""
+        ``horizon - 1``.  ``stride`` (with ``horizon``) is ``model.predict``'s:
+        the frames every window of the rollout contributes."""
         assert eval_frame is not None
+        if stride is not None and horizon is None:
+            raise ValueError("test: stride is the step of a rollout's windows; it needs horizon")
         if horizon is not None and time_tsfm is not None:
             raise ValueError("test: a time transform of a window does not chain over windows; "
                              "horizon needs time_tsfm=None")
@@ -477,7 +480,7 @@ class PredictionEngine:
                 inputs = _to_dev(inputs, dev)
                 all_seqs = all_seqs.float().to(dev, non_blocking=True).contiguous()
                 if horizon is not None:
-                    outputs = self._rollout(inputs, all_seqs, input_n, horizon)
+                    outputs = self._rollout(inputs, all_seqs, input_n, horizon, stride)
                 else:
                     outputs = self.inverse(self.model(self.transform(inputs), False))
                 if isinstance(outputs, list):
@@ -523,7 +526,7 @@ class PredictionEngine:
         return float(t_metric.mean()), t_metric
 
     def test_groups(self, loader, input_n=10, eval_frame=None, joint_to_ignore=None, joint_equal=None,
-                    scale_tsfm=None, horizon=None):
+                    scale_tsfm=None, horizon=None, stride=None):
         """The protocol's whole table in one pass over a resident test set
         whose windows carry a group (an action; dstd_data.DeviceSequences
         ``groups``): what the runners build by one ``test`` per action
@@ -537,8 +540,10 @@ class PredictionEngine:
         the resident frames (dstd_store_group_mpjpe, one launch per batch into
         sums[group][frame] and counts[group] on the device), and the host
         synchronises once, at the end.  The model runs exactly as in ``test``,
-        ``horizon`` included; ``dim_used`` is the set's.  A set without groups
-        is one group named "all"."""
+        ``horizon`` and ``stride`` included; ``dim_used`` is the set's.  A set
+        without groups is one group named "all"."""
+        if stride is not None and horizon is None:
+            raise ValueError("test_groups: stride is the step of a rollout's windows; it needs horizon")
         from dstd_data import DeviceLoader
         if not isinstance(loader, DeviceLoader):
             raise TypeError(f"test_groups: loader must be a dstd_data.DeviceLoader, got {type(loader).__name__}")
@@ -572,7 +577,7 @@ class PredictionEngine:
                 inputs = seqs.gather(idx, outputs=("inputs",))[0]
                 if horizon is not None:
                     observed = self.transform(inputs)[:, :input_n].contiguous()
-                    outputs = self.inverse(self.model.model.predict(observed, horizon))
+                    outputs = self.inverse(self._predict(observed, horizon, stride))
                 else:
                     outputs = self.inverse(self.model(self.transform(inputs), False))
                 if isinstance(outputs, list):
@@ -601,7 +606,14 @@ class PredictionEngine:
             self.logger.info(f"action: {name}|test|loss:{avg_g:.2f}")
         return avg, t_metric, table
 
-    def _rollout(self, inputs, all_seqs, input_n, horizon):
+    def _predict(self, observed, horizon, stride):
+        """``model.predict`` of a rollout evaluation; ``stride`` is handed on
+        only when given, so a model whose predict takes none runs as before."""
+        if stride is None:
+            return self.model.model.predict(observed, horizon)
+        return self.model.model.predict(observed, horizon, stride=stride)
+
+    def _rollout(self, inputs, all_seqs, input_n, horizon, stride=None):
         """test(horizon=...): the model's ``predict`` on the observed frames of
         one batch, in the engine's [n, horizon, dims] form."""
         if isinstance(inputs, list):
@@ -610,7 +622,7 @@ class PredictionEngine:
             raise ValueError(f"test: horizon {horizon} after {input_n} observed frames needs all_seqs of "
                              f"{input_n + horizon} frames, got {all_seqs.shape[1]}")
         observed = self.transform(inputs)[:, :input_n].contiguous()
-        return self.inverse(self.model.model.predict(observed, horizon))
+        return self.inverse(self._predict(observed, horizon, stride))
 
     @staticmethod
     def _presharded_real(sampler):

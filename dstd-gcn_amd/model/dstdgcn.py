@@ -30,6 +30,7 @@ back-propagates through its eval-mode modules; under torch.no_grad() (or
 with frozen parameters and input) eval runs the fused inference kernels.
 """
 import itertools
+import numbers
 import operator
 import math
 import weakref
@@ -1365,7 +1366,7 @@ class DSTDGCN(_NativeModule):
         native.check(code, "dstd_model_fwd_taps")
         return y, out
 
-    def predict(self, observed, horizon=None):
+    def predict(self, observed, horizon=None, stride=None):
         """The ``horizon`` frames (default ``output_time_frame``) that follow
         ``observed`` [N, input_time_frame, V, 3], as [N, horizon, V, 3]: one
         native call (include/dstd_gcn_predict.h) that pads the observed frames
@@ -1377,7 +1378,16 @@ class DSTDGCN(_NativeModule):
         ``self(x)`` over windows built with torch indexing returns, bit for
         bit.  Eval mode only, detached, no autograd; honours ``gc_arithmetic``.
         The folded constants are shared with ``self(x)`` of the same batch
-        size (``_forward_native``)."""
+        size (``_forward_native``).
+
+        ``stride`` (an integer in 1..``output_time_frame``; None or
+        ``output_time_frame``: the chain above, unchanged): every window
+        contributes only its first ``stride`` frames and the next window
+        observes the last ``input_time_frame`` frames known by then, again in
+        one native call (include/ext/dstd_gcn_stride.h) and equal in bits to
+        the window loop.  At most ``PREDICT_MAX_WINDOWS`` windows:
+        ``ceil(horizon / stride) <= 64``.  Eager only: under tracing a stride
+        below ``output_time_frame`` is a NotImplementedError."""
         if self.training:
             raise RuntimeError("DSTDGCN.predict rolls the eval forward out: call .eval() first")
         n, tin, v, c = observed.shape
@@ -1385,10 +1395,15 @@ class DSTDGCN(_NativeModule):
         if c != self.input_channels // 2 or v != self.joints_to_consider:
             raise ValueError(f"DSTDGCN: expected [N, {tin}, {self.joints_to_consider}, {self.input_channels // 2}], "
                              f"got {list(observed.shape)}")
+        stride = self._predict_stride(stride)
         horizon = self.output_time_frame if horizon is None else int(horizon)
         if horizon < 1:
             raise ValueError(f"DSTDGCN.predict: horizon {horizon} < 1")
-        if -(-horizon // self.output_time_frame) > native.PREDICT_MAX_WINDOWS:
+        if -(-horizon // (stride or self.output_time_frame)) > native.PREDICT_MAX_WINDOWS:
+            fits = -(-horizon // native.PREDICT_MAX_WINDOWS)  # the smallest stride with at most that many windows
+            if stride is not None and fits <= self.output_time_frame:
+                raise ValueError(f"DSTDGCN.predict: horizon {horizon} at stride {stride} needs more than "
+                                 f"{native.PREDICT_MAX_WINDOWS} windows; it needs stride >= {fits}")
             raise ValueError(f"DSTDGCN.predict: horizon {horizon} needs more than {native.PREDICT_MAX_WINDOWS} "
                              f"windows of {self.output_time_frame} frames")
         native.lib()
@@ -1396,24 +1411,48 @@ class DSTDGCN(_NativeModule):
         native.require_device(observed, "observed")
         flags = native.arith_flags(self.gc_arithmetic)
         if type(observed) is not torch.Tensor or torch.compiler.is_compiling():
+            if stride is not None:
+                raise NotImplementedError("DSTDGCN.predict: a stride below output_time_frame is eager only -- the "
+                                          "custom op has no stride, so it cannot be traced (torch.compile, tensor "
+                                          "subclasses)")
             # tracing: the custom op, whose inputs name every tensor the call reads
             params, buffers = self._tree.get(self)
             return torch.ops.dstd.dstdgcn_predict(observed, params + buffers, self._dstd_uid, horizon, flags)
         with torch.no_grad():
             out = observed.new_empty(n, horizon, v, c)
             if n:
-                self._predict_native(observed, out, arith=flags)
+                self._predict_native(observed, out, arith=flags, stride=stride)
         return out
 
-    def _predict_native(self, obs, out, arith=None):
-        """One rollout through dstd_model_predict, on the forward's workspace
-        and constants (``_claim_workspace``)."""
+    def _predict_stride(self, stride):
+        """``predict``'s ``stride`` as checked: None for today's chain (no
+        stride, or one of a whole window), the integer otherwise."""
+        if stride is None:
+            return None
+        if isinstance(stride, bool) or not isinstance(stride, numbers.Integral) \
+                or not 1 <= stride <= self.output_time_frame:
+            raise ValueError(f"DSTDGCN.predict: stride must be an integer in 1..{self.output_time_frame} "
+                             f"(output_time_frame), got {stride!r}")
+        return None if stride == self.output_time_frame else int(stride)
+
+    def _predict_native(self, obs, out, arith=None, stride=None):
+        """One rollout through dstd_model_predict -- with a ``stride``,
+        dstd_model_predict_strided -- on the forward's workspace and constants
+        (``_claim_workspace``)."""
         L = native.lib()
         n, tin, v, _ = obs.shape
         dev = obs.device
         t = tin + self.output_time_frame
         p = self._native_params()
         flags = (native.arith_flags(self.gc_arithmetic) if arith is None else arith) | self._dstd_fwd_flags
+        if stride is not None:
+            nbytes = L.dstd_model_predict_strided_workspace_bytes(n, t, v, self.num_feature, self.num_layers)
+            ws, flags = self._claim_workspace(dev, nbytes, n, flags)
+            code = L.dstd_model_predict_strided(native.ext_stride.model_params_ref(p), native.ptr(obs, "observed"), n,
+                                                tin, out.shape[1], stride, native.ptr(out, "out"), ws.data_ptr(),
+                                                ws.numel(), native.stream_handle(dev), flags)
+            native.check(code, "dstd_model_predict_strided")
+            return
         nbytes = L.dstd_model_predict_workspace_bytes(n, t, v, self.num_feature, self.num_layers)
         ws, flags = self._claim_workspace(dev, nbytes, n, flags)
         code = L.dstd_model_predict(p, native.ptr(obs, "observed"), n, tin, out.shape[1], native.ptr(out, "out"),

@@ -447,16 +447,18 @@ class DSTDGCN(_Shadowed):
         self._sync(sh)
         return sh(x)
 
-    def predict(self, observed, horizon=None):
+    def predict(self, observed, horizon=None, stride=None):
         """``dstdgcn.DSTDGCN.predict`` through the shadow model: the ``horizon``
         frames after ``observed`` [N, input_time_frame, V, 3] in one native
-        call.  Eval mode only, detached."""
+        call, ``stride`` frames kept per window (None: all of them).  Eval
+        mode only, detached."""
         if self.training:
             raise RuntimeError("DSTDGCN.predict rolls the eval forward out: call .eval() first")
+        base.DSTDGCN._predict_stride(self, stride)  # a bad stride is refused before the device is asked for
         native.require_device(observed, "observed")
         sh = self._shadow_for(observed.device)
         self._sync(sh)
-        return sh.predict(observed, horizon)
+        return sh.predict(observed, horizon, stride)
 
     def forward_pair(self, x1, x2):
         """``(self(x1), self(x2))`` as one paired native train step
