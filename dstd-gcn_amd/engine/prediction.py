@@ -215,7 +215,7 @@ class PredictionEngine:
 
     # ------------------------------------------------------------------
     def train(self, train_loader, epoch, time_tsfm=None, scale_tsfm=None, weights=None, max_iter=-1, horizon=None,
-              teacher_ratio=0.0):
+              teacher_ratio=0.0, stride=None):
         """``horizon`` (None: the reference's path, one forward of the padded
         window): train through a rollout instead -- the first
         ``input_time_frame`` frames of ``inputs`` (and of ``inputs_inv``) are the
@@ -232,7 +232,15 @@ class PredictionEngine:
         the ground-truth frames of ``targets`` as its next window with this
         probability, drawn on the device from torch's generator, and no
         gradient crosses such a boundary.  It holds for this call: anneal it
-        from 1 towards 0 over the epochs."""
+        from 1 towards 0 over the epochs.
+
+        ``stride`` (with ``horizon``; None: whole windows, the step as it is
+        without the argument) is ``model.rollout``'s: every window hands on its
+        first ``stride`` frames, the chain ``test(horizon=, stride=)``
+        evaluates, and the mask of ``teacher_ratio`` has
+        ``ceil(horizon / stride)`` rows."""
+        if stride is not None and horizon is None:
+            raise ValueError("train: stride is the step of a rollout's windows; it needs horizon")
         if horizon is not None and time_tsfm is not None:
             raise ValueError("train: a time transform of a window does not chain over windows; "
                              "horizon needs time_tsfm=None")
@@ -264,12 +272,12 @@ class PredictionEngine:
         net._dstd_inplace_grads = True
         try:
             return self._train_epoch(train_loader, epoch, time_tsfm, scale_tsfm, weights, max_iter, t_l, horizon,
-                                     teacher_ratio)
+                                     teacher_ratio, *((stride,) if stride is not None else ()))
         finally:
             net._dstd_inplace_grads = prev_inplace
 
     def _train_epoch(self, train_loader, epoch, time_tsfm, scale_tsfm, weights, max_iter, t_l, horizon=None,
-                     teacher_ratio=0.0):
+                     teacher_ratio=0.0, stride=None):
         dev = self.device
         distributed = _world()[1] > 1
         num_iter = len(train_loader) if max_iter == -1 else min(len(train_loader), max_iter)
@@ -279,6 +287,9 @@ class PredictionEngine:
 
             def step(inp, inp_inv, targ):
                 if horizon is not None:
+                    if stride is not None:
+                        return self._step_rollout(inp, inp_inv, targ, horizon, scale_tsfm, weights, distributed,
+                                                  teacher_ratio, stride)
                     return self._step_rollout(inp, inp_inv, targ, horizon, scale_tsfm, weights, distributed,
                                               *((teacher_ratio,) if teacher_ratio > 0 else ()))
                 return self._step(inp, inp_inv, targ, time_tsfm, scale_tsfm, weights, distributed)
@@ -391,7 +402,8 @@ class PredictionEngine:
         self.optimizer.step()
         return tuple(loss[ls].detach() for ls in self.config["loss"])
 
-    def _step_rollout(self, inputs, inputs_inv, targets, horizon, scale_tsfm, weights, distributed, teacher_ratio=0.0):
+    def _step_rollout(self, inputs, inputs_inv, targets, horizon, scale_tsfm, weights, distributed, teacher_ratio=0.0,
+                      stride=None):
         """One training step through a rollout (train(horizon=...)): the
         observed frames of the batch (and of its time reversal) rolled out
         ``horizon`` frames by one native chain, every loss line of both passes
@@ -401,7 +413,8 @@ class PredictionEngine:
         gradient all-reduce / clip and Adam as ``_step``.  ``teacher_ratio`` > 0:
         scheduled sampling -- a mask [windows, samples of both passes] drawn on
         the device (no synchronisation) and ``targets`` as the teacher of both
-        passes, the reversal reading it backwards."""
+        passes, the reversal reading it backwards.  ``stride``: the chain's
+        (``model.rollout``); the mask then has ``ceil(horizon / stride)`` rows."""
         net = self.model.model
         input_n = net.input_time_frame
         pair = bool(self.config["inverse"])
@@ -415,10 +428,12 @@ class PredictionEngine:
                                  f"{input_n + horizon} frames, got {x.shape[1]}")
         observed = self.transform(inputs)[:, :input_n].contiguous()
         tf = {}
+        if stride is not None:
+            tf["stride"] = stride = net._predict_stride(stride, "rollout")
         if teacher_ratio > 0:
-            windows = -(-horizon // net.output_time_frame)
+            windows = -(-horizon // (stride or net.output_time_frame))
             drawn = torch.rand(windows, observed.shape[0] * (2 if pair else 1), device=observed.device)
-            tf = dict(teacher=self.transform(targets), teacher_mask=drawn < teacher_ratio)
+            tf.update(teacher=self.transform(targets), teacher_mask=drawn < teacher_ratio)
         if pair:
             observed_inv = self.transform(inputs_inv)[:, :input_n].contiguous()
             preds = [self.inverse(o) for o in net.rollout_pair(observed, observed_inv, horizon, **tf)]

@@ -822,6 +822,136 @@ class _RolloutTeacherPair(torch.autograd.Function):
         return _RolloutTeacher.backward(ctx, torch.cat([d1, d2]))
 
 
+class _RolloutStrided(torch.autograd.Function):
+    """DSTDGCN.rollout with a stride below ``output_time_frame``
+    (include/ext/dstd_gcn_stride_train.h): every window hands on its first
+    ``stride`` frames, and the chain and its backward are again two native
+    calls.  One Function with or without a teacher -- the entry points take the
+    teacher's arguments as NULL for a free-running chain; ``teacher``, ``mask``
+    and ``maps`` are None then.  Flags, seeds, saved, the anchored parameters,
+    both gradient modes and what is returned to autograd are _RolloutTeacher's,
+    with ``ceil(horizon / stride)`` windows."""
+
+    @staticmethod
+    def forward(ctx, model, paired, horizon, stride, obs, teacher, mask, maps, *params):
+        L = native.lib()
+        n, tin, v, c = obs.shape
+        dev = obs.device
+        t = tin + model.output_time_frame
+        windows = -(-horizon // stride)
+        flags = _bn_flags(model) | (native.TRAIN_PAIRED if paired else 0)
+        if getattr(model, "_dstd_one_stream", False):
+            flags |= native.TRAIN_ONE_STREAM
+        drop = float(model.do_in.p) if model.do_in.training else 0.0
+        seeds, ctx.seed_t = None, None
+        if drop > 0:
+            ctx.seed_t = torch.randint(0, 2 ** 62, (windows,), device=dev, dtype=torch.int64)
+            seeds = ctx.seed_t.data_ptr()
+            flags |= native.TRAIN_SEED_DEVICE
+        params_all, buffers = model._tree.get(model)
+        out = obs.new_empty(n, horizon, v, c)
+        nbytes = L.dstd_model_rollout_saved_bytes(n, t, v, model.num_feature, model.num_layers, windows)
+        saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ctx.mask = mask  # the backward reads it again
+        if mask is None:
+            ctx.tf = (None, 0, None, None, None)
+        else:
+            ctx.tf = (native.ptr(teacher, "teacher"), teacher.shape[1], *native.ext_stride_train.frame_maps(maps),
+                      mask.data_ptr())
+        code = L.dstd_model_rollout_strided_fwd(native.ext_stride_train.model_params_ref(model._native_params()),
+                                                native.ptr(obs, "observed"), n, tin, horizon, stride,
+                                                _bn_momentum(model), drop, seeds, native.ptr(out, "out"),
+                                                saved.data_ptr(), nbytes, *ctx.tf, native.stream_handle(dev), flags)
+        native.check(code, "dstd_model_rollout_strided_fwd")
+        if not flags & native.TRAIN_RUNNING_STATS:
+            torch.autograd.graph.increment_version(buffers)
+            _count_batch(model, windows * (2 if paired else 1))
+        ctx.model, ctx.saved_buf, ctx.drop, ctx.flags, ctx.shape = model, saved, drop, flags, (n, tin, v, c)
+        ctx.horizon, ctx.stride = horizon, stride
+        ctx.anchored = len(params) == 1 and params[0] is getattr(model, "_dstd_anchor_t", None)
+        ctx.params = params_all if ctx.anchored else list(params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = native.lib()
+        model = ctx.model
+        n, tin, v, c = ctx.shape
+        dev = dout.device
+        dout = dout.contiguous()
+        need_dx = bool(ctx.needs_input_grad[4])
+        if ctx.saved_buf is None:
+            raise RuntimeError("DSTDGCN.rollout: backward through the chain a second time "
+                               "(its saved windows were freed by the first)")
+        arena, direct = None, False
+        if ctx.anchored or (getattr(model, "_dstd_inplace_grads", False) and not _param_hooks(ctx.params)):
+            arena, direct = native.grad_sink(model, ctx.params, dev)
+        t = tin + model.output_time_frame
+        windows = -(-ctx.horizon // ctx.stride)
+        ws = native.workspace(dev, L.dstd_model_rollout_strided_workspace_bytes(n, t, v, model.num_feature,
+                                                                                model.num_layers, tin, ctx.horizon))
+        dobs = dout.new_empty(n, tin, v, c) if need_dx else None
+        pref = native.ext_stride_train.model_params_ref(model._native_params())
+        tail = (ctx.drop, ctx.seed_t.data_ptr() if ctx.seed_t is not None else None, ctx.saved_buf.data_ptr(),
+                ctx.saved_buf.numel(), native.ptr(dout, "dout"))
+        tail2 = (dobs.data_ptr() if need_dx else None, ws.data_ptr(), ws.numel(), *ctx.tf, native.stream_handle(dev),
+                 ctx.flags)
+        gref = native.ext_stride_train.model_grads_ref
+        if direct:  # one (+=) chain into the parameters' .grad
+            g = getattr(arena, "model_grads", None)
+            if g is None:
+                g = arena.model_grads = model._native_grads(arena)
+            code = L.dstd_model_rollout_strided_bwd(pref, n, tin, ctx.horizon, ctx.stride, *tail, gref(g), *tail2)
+            native.check(code, "dstd_model_rollout_strided_bwd")
+        else:  # an arena per window, summed in backward order (_RolloutTrain.backward says why)
+            numel = native.arena_numel(ctx.params)
+            bufs = torch.zeros(windows, numel, dtype=torch.float32, device=dev)
+            for k in range(windows - 1, -1, -1):
+                g = model._native_grads(native.GradArena(ctx.params, dev, buf=bufs[k]))
+                code = L.dstd_model_rollout_strided_bwd_window(pref, n, tin, ctx.horizon, ctx.stride, k, *tail, gref(g),
+                                                               *tail2)
+                native.check(code, "dstd_model_rollout_strided_bwd_window")
+            total = bufs[windows - 1]
+            for k in range(windows - 2, -1, -1):
+                total += bufs[k]
+            arena = native.GradArena(ctx.params, dev, buf=total)
+        ctx.saved_buf = ctx.seed_t = ctx.mask = ctx.tf = None
+        # model, paired, horizon, stride, obs, teacher, mask, maps
+        head = (None, None, None, None, dobs, None, None, None)
+        if direct:
+            return (*head, *([None] * (1 if ctx.anchored else len(arena.params))))
+        if ctx.anchored:
+            for p, gv in zip(arena.params, arena.views()):
+                if gv is not None and p.requires_grad:
+                    if p.grad is None:
+                        p.grad = gv.clone()
+                    else:
+                        p.grad.add_(gv)
+            return (*head, None)
+        return (*head, *arena.views())
+
+
+class _RolloutStridedPair(torch.autograd.Function):
+    """_RolloutTrainPair over _RolloutStrided."""
+
+    @staticmethod
+    def forward(ctx, model, n, horizon, stride, obs, teacher, mask, maps, *params):
+        out = _RolloutStrided.forward(ctx, model, True, horizon, stride, obs, teacher, mask, maps, *params)
+        ctx.half = n
+        return out[:n], out[n:]
+
+    @staticmethod
+    def backward(ctx, d1, d2):
+        n2, tin, v, c = ctx.shape
+        n = ctx.half
+        ref = d1 if d1 is not None else d2
+        if d1 is None:
+            d1 = ref.new_zeros((n, ctx.horizon, v, c))
+        if d2 is None:
+            d2 = ref.new_zeros((n2 - n, ctx.horizon, v, c))
+        return _RolloutStrided.backward(ctx, torch.cat([d1, d2]))
+
+
 class BatchNorm(nn.Module):
     """BN1d over C*V channels of an NCTV tensor (reference :35-50).  Glue only:
     on the hot path every BatchNorm is folded into a kernel epilogue."""
@@ -1424,14 +1554,15 @@ class DSTDGCN(_NativeModule):
                 self._predict_native(observed, out, arith=flags, stride=stride)
         return out
 
-    def _predict_stride(self, stride):
-        """``predict``'s ``stride`` as checked: None for today's chain (no
-        stride, or one of a whole window), the integer otherwise."""
+    def _predict_stride(self, stride, what="predict"):
+        """``predict``'s (and ``rollout``'s) ``stride`` as checked: None for
+        today's chain (no stride, or one of a whole window), the integer
+        otherwise."""
         if stride is None:
             return None
         if isinstance(stride, bool) or not isinstance(stride, numbers.Integral) \
                 or not 1 <= stride <= self.output_time_frame:
-            raise ValueError(f"DSTDGCN.predict: stride must be an integer in 1..{self.output_time_frame} "
+            raise ValueError(f"DSTDGCN.{what}: stride must be an integer in 1..{self.output_time_frame} "
                              f"(output_time_frame), got {stride!r}")
         return None if stride == self.output_time_frame else int(stride)
 
@@ -1459,8 +1590,9 @@ class DSTDGCN(_NativeModule):
                                     ws.data_ptr(), ws.numel(), native.stream_handle(dev), flags)
         native.check(code, "dstd_model_predict")
 
-    def _rollout_args(self, observed, horizon, what):
-        """(observed's shape, horizon) of a rollout call, checked as ``predict`` checks them."""
+    def _rollout_args(self, observed, horizon, what, stride=None):
+        """(observed's shape, horizon) of a rollout call, checked as ``predict``
+        checks them; ``stride``: what ``_predict_stride`` returned."""
         n, tin, v, c = observed.shape
         assert tin == self.input_time_frame
         if c != self.input_channels // 2 or v != self.joints_to_consider:
@@ -1469,7 +1601,11 @@ class DSTDGCN(_NativeModule):
         horizon = self.output_time_frame if horizon is None else int(horizon)
         if horizon < 1:
             raise ValueError(f"DSTDGCN.{what}: horizon {horizon} < 1")
-        if -(-horizon // self.output_time_frame) > native.PREDICT_MAX_WINDOWS:
+        if -(-horizon // (stride or self.output_time_frame)) > native.PREDICT_MAX_WINDOWS:
+            fits = -(-horizon // native.PREDICT_MAX_WINDOWS)  # the smallest stride with at most that many windows
+            if stride is not None and fits <= self.output_time_frame:
+                raise ValueError(f"DSTDGCN.{what}: horizon {horizon} at stride {stride} needs more than "
+                                 f"{native.PREDICT_MAX_WINDOWS} windows; it needs stride >= {fits}")
             raise ValueError(f"DSTDGCN.{what}: horizon {horizon} needs more than {native.PREDICT_MAX_WINDOWS} "
                              f"windows of {self.output_time_frame} frames")
         return (n, tin, v, c), horizon
@@ -1485,16 +1621,17 @@ class DSTDGCN(_NativeModule):
         native.lib()
         native.require_device(observed, "observed")
 
-    def _teacher_args(self, teacher, teacher_mask, observed, halves, horizon, what):
+    def _teacher_args(self, teacher, teacher_mask, observed, halves, horizon, what, stride=None):
         """(teacher, mask as uint8) of a rollout call with scheduled sampling,
         checked before anything runs: ``teacher`` [N, >= input_n + horizon, V, 3]
         float32 and ``teacher_mask`` [windows, halves * N] bool or uint8, both
-        on the device of ``observed`` [N, input_n, V, 3]."""
+        on the device of ``observed`` [N, input_n, V, 3]; ``windows`` is
+        ``ceil(horizon / stride)`` with a ``stride``."""
         if (teacher is None) != (teacher_mask is None):
             raise ValueError(f"DSTDGCN.{what}: teacher and teacher_mask come together "
                              f"(got {'teacher' if teacher_mask is None else 'teacher_mask'} alone)")
         n, tin, v, c = observed.shape
-        windows = -(-horizon // self.output_time_frame)
+        windows = -(-horizon // (stride or self.output_time_frame))
         for name, x in (("teacher", teacher), ("teacher_mask", teacher_mask)):
             if not torch.is_tensor(x):
                 raise ValueError(f"DSTDGCN.{what}: {name} must be a tensor, got {type(x).__name__}")
@@ -1516,7 +1653,7 @@ class DSTDGCN(_NativeModule):
         mask = teacher_mask.contiguous()
         return teacher.detach().contiguous(), mask.view(torch.uint8) if mask.dtype == torch.bool else mask
 
-    def rollout(self, observed, horizon=None, teacher=None, teacher_mask=None):
+    def rollout(self, observed, horizon=None, teacher=None, teacher_mask=None, stride=None):
         """``predict`` that autograd can differentiate and a train-mode model
         can run: the ``horizon`` frames (default ``output_time_frame``) after
         ``observed`` [N, input_time_frame, V, 3], as [N, horizon, V, 3].
@@ -1542,27 +1679,47 @@ class DSTDGCN(_NativeModule):
         window k is built from the teacher's frames instead of what is known
         so far wherever ``teacher_mask[k, b]`` is set, and no gradient crosses
         that boundary (include/ext/dstd_gcn_teacher.h; row 0 is not read).  The
-        result is always the model's prediction.  Neither gets a gradient."""
-        (n, tin, v, c), horizon = self._rollout_args(observed, horizon, "rollout")
+        result is always the model's prediction.  Neither gets a gradient.
+
+        ``stride`` is ``predict``'s (an integer in 1..``output_time_frame``;
+        None or ``output_time_frame``: the chain above, call for call): every
+        window hands on its first ``stride`` frames only, so the chain has
+        ``ceil(horizon / stride)`` windows -- at most ``PREDICT_MAX_WINDOWS``,
+        and that many rows of ``teacher_mask`` -- and a predicted frame is
+        observed by up to ``ceil(input_time_frame / stride)`` later windows,
+        whose gradients are summed in a fixed order
+        (include/ext/dstd_gcn_stride_train.h).  What the window loop of
+        ``predict(stride=)`` computes under autograd, bit for bit
+        (tests/test_gpu_rollout_stride.py).  As without a stride, the frames
+        a forced window took from the teacher are what that sample knows from
+        then on: a later free window that still observes them sees the
+        teacher's frames, and no gradient passes through them.  Its saved
+        activations grow with the number of windows, not with ``horizon``."""
+        stride = self._predict_stride(stride, "rollout")
+        (n, tin, v, c), horizon = self._rollout_args(observed, horizon, "rollout", stride)
         params = self._tree.get(self)[0]
         tf = teacher is not None or teacher_mask is not None
         if tf:
-            teacher, mask = self._teacher_args(teacher, teacher_mask, observed, 1, horizon, "rollout")
+            teacher, mask = self._teacher_args(teacher, teacher_mask, observed, 1, horizon, "rollout", stride)
         if not self.training and not _needs_grad(observed, *params):
             if tf:
                 raise RuntimeError("DSTDGCN.rollout: a teacher needs train mode or something to differentiate "
                                    "(predict has no teacher)")
-            return self.predict(observed, horizon)
+            return self.predict(observed, horizon, stride)
         self._rollout_refusals(observed, "rollout")
         observed = observed.contiguous()
         if n == 0:  # empty batch: empty output
             return _mark(observed.new_empty(0, horizon, v, c), observed, *params)
+        if stride is not None:
+            return _RolloutStrided.apply(self, False, horizon, stride, observed, teacher if tf else None,
+                                         mask if tf else None, [(0, 1)] if tf else None,
+                                         *_anchor_of(self, observed, params))
         if tf:
             return _RolloutTeacher.apply(self, False, horizon, observed, teacher, mask, [(0, 1)],
                                          *_anchor_of(self, observed, params))
         return _RolloutTrain.apply(self, False, horizon, observed, *_anchor_of(self, observed, params))
 
-    def rollout_pair(self, obs1, obs2, horizon=None, teacher=None, teacher_mask=None):
+    def rollout_pair(self, obs1, obs2, horizon=None, teacher=None, teacher_mask=None, stride=None):
         """``(self.rollout(obs1, horizon), self.rollout(obs2, horizon))`` as one
         chain over the concatenated batch, as ``forward_pair`` is for one
         window: in train mode every window keeps each half's own batch
@@ -1574,25 +1731,30 @@ class DSTDGCN(_NativeModule):
         obs1's forwards in time and obs2's backwards from its last frame (the
         time reversal of PredictionEngine.train: frame maps (0, +1) and
         (Ttot - 1, -1)); ``teacher_mask`` is [windows, 2 N], obs1's samples
-        first."""
+        first.  ``stride`` is ``rollout``'s."""
+        stride = self._predict_stride(stride, "rollout_pair")
         tf = teacher is not None or teacher_mask is not None
         if tf:
             if obs1.shape != obs2.shape or obs1.device != obs2.device:
                 raise ValueError("DSTDGCN.rollout_pair: one teacher serves two batches of one shape on one device, got "
                                  f"{list(obs1.shape)} on {obs1.device} and {list(obs2.shape)} on {obs2.device}")
-            (n, tin, v, c), horizon = self._rollout_args(obs1, horizon, "rollout_pair")
-            teacher, mask = self._teacher_args(teacher, teacher_mask, obs1, 2, horizon, "rollout_pair")
+            (n, tin, v, c), horizon = self._rollout_args(obs1, horizon, "rollout_pair", stride)
+            teacher, mask = self._teacher_args(teacher, teacher_mask, obs1, 2, horizon, "rollout_pair", stride)
         if not self.training or obs1.shape != obs2.shape or obs1.shape[0] == 0 or obs1.device != obs2.device:
             if tf:  # the second call reads the teacher backwards as a tensor of its own
-                return (self.rollout(obs1, horizon, teacher, mask[:, :n]),
-                        self.rollout(obs2, horizon, teacher.flip(1), mask[:, n:]))
-            return self.rollout(obs1, horizon), self.rollout(obs2, horizon)
-        (n, tin, v, c), horizon = self._rollout_args(obs1, horizon, "rollout_pair")
+                return (self.rollout(obs1, horizon, teacher, mask[:, :n], stride=stride),
+                        self.rollout(obs2, horizon, teacher.flip(1), mask[:, n:], stride=stride))
+            return self.rollout(obs1, horizon, stride=stride), self.rollout(obs2, horizon, stride=stride)
+        (n, tin, v, c), horizon = self._rollout_args(obs1, horizon, "rollout_pair", stride)
         self._rollout_refusals(obs1, "rollout_pair")
         if type(obs2) is not torch.Tensor:
             raise RuntimeError("DSTDGCN.rollout_pair: eager only (tensor subclasses cannot be traced through the chain)")
         obs = torch.cat([obs1, obs2]).contiguous()
         params = self._tree.get(self)[0]
+        if stride is not None:
+            maps = [(0, 1), (teacher.shape[1] - 1, -1)] if tf else None
+            return _RolloutStridedPair.apply(self, n, horizon, stride, obs, teacher if tf else None,
+                                             mask if tf else None, maps, *_anchor_of(self, obs, params))
         if tf:
             return _RolloutTeacherPair.apply(self, n, horizon, obs, teacher, mask, [(0, 1), (teacher.shape[1] - 1, -1)],
                                              *_anchor_of(self, obs, params))
