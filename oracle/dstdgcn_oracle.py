@@ -113,7 +113,8 @@ def dstdgcb(x, p, training=False):
 
 
 def dstdgcn(x, sd, num_layers, dtype=torch.float64, training=False, device="cpu"):
-    """DSTDGCN.forward (model/dstdgcn.py:293-317), dropout treated as eval.
+    """DSTDGCN.forward (model/dstdgcn.py:293-317); do_in dropout (:309) is the
+    identity here (eval), dstdgcn_fn takes a mask.
 
     x: [N, T, V, 3]; sd: reference state dict (numpy or tensors).  ``device``
     other than the CPU only serves scripts/parity_report.py (the reference
@@ -122,12 +123,18 @@ def dstdgcn(x, sd, num_layers, dtype=torch.float64, training=False, device="cpu"
     return dstdgcn_fn(_t(x, dtype, device), sd, num_layers, training)
 
 
-def dstdgcn_fn(x, sd, num_layers, training=False):
-    """dstdgcn() on tensors used as given (autograd flows through them)."""
+def dstdgcn_fn(x, sd, num_layers, training=False, drop=None):
+    """dstdgcn() on tensors used as given (autograd flows through them).
+
+    ``drop``: do_in dropout (:309) with a given mask -- a tensor [N, C, T, V]
+    that already holds keep * 1 / (1 - p) and multiplies the activation between
+    bn_in / prelu and the encoders.  None: no dropout (eval, or p = 0)."""
     residual = x[:, -1:]                                              # :299
     h = torch.cat((x, x - residual), dim=-1).permute(0, 3, 1, 2)      # :298-303
     h = dstdgcb(h, sub(sd, "conv_st_in.stgcn.0.0."), training)        # :305 (residual=None)
     h = prelu(batchnorm(h, sub(sd, "bn_in.bn."), training), sd["prelu.weight"])   # :306-308
+    if drop is not None:                                              # :309 do_in
+        h = h * drop
     for i in range(num_layers):                                       # :310-311, 278-285
         e = f"encoders.{i}."
         y = dstdgcb(h, sub(sd, e + "0.stgcn.0.0."), training) + h     # Identity residual :247-248
@@ -233,13 +240,16 @@ def fast_dstdgcb(x, p, training=False):
     return fast_dstdgc(h, sub(p, "conv_t.0."), a_t, p["alpha_tm"], "temporal")
 
 
-def fast_dstdgcn_fn(x, sd, num_layers, training=False):
+def fast_dstdgcn_fn(x, sd, num_layers, training=False, drop=None):
     """dstdgcn_fast.DSTDGCN.forward (model/dstdgcn_fast.py:548-614) on
-    tensors used as given; dropout treated as eval."""
+    tensors used as given.  ``drop``: the do_in mask times its scale as in
+    dstdgcn_fn, in this function's layout [N, T, V, C]; None: no dropout."""
     residual = x[:, -1:]                                              # :555
     h = torch.cat((x, x - residual), dim=-1)                          # :558-559 (stays NTVC)
     h = fast_dstdgcb(h, sub(sd, "conv_st_in.stgcn.0.0."), training)   # :563
     h = prelu(fast_batchnorm(h, sub(sd, "bn_in.bn."), training), sd["prelu.weight"])   # :570-572
+    if drop is not None:                                              # do_in
+        h = h * drop
     for i in range(num_layers):                                       # :583-584
         e = f"encoders.{i}."
         y = fast_dstdgcb(h, sub(sd, e + "0.stgcn.0.0."), training) + h
@@ -307,21 +317,24 @@ def train_params(sd0, dtype=torch.float64, device="cpu"):
     return P
 
 
-def step_loss(P, batch, num_layers, inverse=True):
+def step_loss(P, batch, num_layers, inverse=True, drops=None):
     """Losses of one PredictionEngine.train step (prediction.py:231-287):
     returns (loss, all_loss) with all_loss = (loss + loss_inv) / 2 when
-    ``inverse``.  A_s re-reads R_s's values (the storage alias, :107-109)."""
+    ``inverse``.  A_s re-reads R_s's values (the storage alias, :107-109).
+    ``drops``: (mask of the forward pass, mask of the inverse pass) as
+    dstdgcn_fn's ``drop``."""
     p0 = next(iter(P.values()))
     inp, inv, seq = (_t(a, p0.dtype, p0.device) for a in batch)
     B, T, VC = inp.shape
+    d_fwd, d_inv = (None, None) if drops is None else (_t(a, p0.dtype, p0.device) for a in drops)
     for k in list(P):
         if k.endswith(".A_s"):
             P[k] = P[k[:-3] + "R_s"].detach()
-    out = dstdgcn_fn(inp.view(B, T, VC // 3, 3), P, num_layers, training=True).reshape(B, T, VC)
+    out = dstdgcn_fn(inp.view(B, T, VC // 3, 3), P, num_layers, training=True, drop=d_fwd).reshape(B, T, VC)
     loss = mpjpe_error_3d(out, seq)
     if not inverse:
         return loss, loss
-    out_i = dstdgcn_fn(inv.view(B, T, VC // 3, 3), P, num_layers, training=True).reshape(B, T, VC)
+    out_i = dstdgcn_fn(inv.view(B, T, VC // 3, 3), P, num_layers, training=True, drop=d_inv).reshape(B, T, VC)
     return loss, (loss + mpjpe_error_3d(out_i, seq.flip(1))) / 2
 
 

@@ -697,8 +697,8 @@ def test_model_train(T, V, flags, B, drop, need_dx):
             for j, (s1, s2) in enumerate(((m1, m2), (v1, v2))):
                 want = 0.9 * (0.9 * old[2 * i + j].double().cpu() + 0.1 * s1) + 0.1 * s2
                 assert rel(stats[2 * i + j], want) < tol, (what, i, j)
-    # (dropout: the mask is a hash of the seed with no host restatement, so those cases are held by
-    # finiteness and bit identity across the fills)
+    # (dropout: held here by finiteness and bit identity across the fills; the mask restated on the host and the
+    # step against the fp64 oracle with it: tests/dropout_helper.py, tests/test_gpu_dropout.py)
 
 
 # =====================================================================================

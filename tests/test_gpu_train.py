@@ -318,16 +318,24 @@ MAX_RATIO = 3.0
 MAX_RATIO_GLOBAL = 4.0
 
 
-def fp32_noise(sd0, batch, g64, extra=None, n_orders=N_ORDERS):
+def fp32_noise(sd0, batch, g64, extra=None, n_orders=N_ORDERS, step=None):
     """Per tensor: the largest |g32 - g64| over the fp32 oracle step on the
     CPU, on the GPU and on the GPU over n_orders sample orders of ``batch``
     (numpy (inp, inv, seq)); ``extra``: more per-tensor fp32 errors (the
-    reference's own, train_grads.npz g32err)."""
+    reference's own, train_grads.npz g32err).  ``step(device, perm)``: another
+    fp32 step than the engine's (tests/test_gpu_dropout.py: a random upstream
+    gradient and dropout masks whose rows travel with their samples) --
+    {tensor: its fp32 result as float64 numpy, in g64's sample order}; of
+    ``batch`` only the sample count is read then."""
     B = batch[0].shape[0]
     runs = [("cpu", None), (DEV, None)] + [(DEV, np.random.default_rng(s).permutation(B))
                                            for s in range(1, n_orders + 1)]
     noise = {k: float(extra[k]) if extra is not None else 0.0 for k in g64}
     for dev, perm in runs:
+        if step is not None:
+            for k, v in step(dev, perm).items():
+                noise[k] = max(noise[k], float(np.abs(v - g64[k]).max()))
+            continue
         P = O.train_params(sd0, torch.float32, dev)
         _, lall = O.step_loss(P, batch if perm is None else tuple(x[perm] for x in batch), 5)
         lall.backward()
@@ -735,8 +743,25 @@ def test_graphed_engine_test_after_replays():
 
 def test_dropout_mask_is_regenerated_in_backward():
     """do_in dropout (p > 0): the forward mask is a hash of (seed, element),
-    so the backward regenerates it; the gradient matches a finite difference
-    along a random direction of the input-layer weights."""
+    so the backward regenerates it.
+
+    The gradient of the last block's PReLU slope matches a central finite
+    difference.  That slope sits after do_in: its gradient holds the forward
+    mask and the seed fixed but never meets the backward's mask.  The
+    model-level slope in front of do_in does -- its gradient is the backward's
+    masked dha summed -- but no finite difference reaches it on this model:
+    through the five encoder blocks the loss is so curved in that slope that
+    the fp64 oracle's own central difference is +1.5e5 at eps 1e-2, -2.6e5 at
+    1e-3, -3.4e5 at 1e-4 and -4.7e5 at 1e-5 against an analytic -4.39e5 (first
+    agreeing, to 7e-4, at 1e-6, where an fp32 forward resolves nothing); the
+    native step: fd 1.49e5 at eps 1e-2 against a gradient of 1.88e6 under its
+    own draw.  So that slope, with y, dx and every other gradient, is held
+    against the fp64 oracle run with the mask restated on the host
+    (tests/dropout_helper.py), under the whole-model criterion: a backward
+    that skipped the mask, drew another or scaled it otherwise moves them far
+    beyond it (tests/test_dropout_host.py; more shapes and paths:
+    tests/test_gpu_dropout.py)."""
+    from dropout_helper import drawn_seeds, drop_tensor, oracle_step
     m, d = _model_3dpw()
     m.do_in.p = 0.3
     x = torch.from_numpy(d["train/inp0"]).to(DEV).view(8, 40, 23, 3)
@@ -751,8 +776,11 @@ def test_dropout_mask_is_regenerated_in_backward():
     assert not torch.equal(y1, y3)
     # gradient w.r.t. the last block's PReLU slope (after do_in) vs finite differences
     p = m.conv_st_out.stgcn[0][0].prelu.weight
-    torch.manual_seed(5)
-    (m(x) * w).sum().backward()
+    (seed,) = drawn_seeds(5, DEV)  # (the generators as torch.manual_seed(5) leaves them)
+    xg = x.clone().requires_grad_(True)
+    yg = m(xg)
+    assert torch.equal(yg, y1)
+    (yg * w).sum().backward()
     gp = float(p.grad)
     eps = 1e-2
     vals = []
@@ -766,6 +794,16 @@ def test_dropout_mask_is_regenerated_in_backward():
             p.sub_(s)
     fd = (vals[0] - vals[1]) / (2 * eps)
     assert abs(fd - gp) <= 2e-2 * max(abs(fd), 1.0), (fd, gp)
+    # the slope in front of do_in, and everything else, against the masked fp64 oracle
+    sd0 = group(d, "train/sd0/")
+    xs, ws, drops = [x.cpu()], [w.cpu()], [drop_tensor(seed, (8, 64, 40, 23), 0.3)]
+    g64 = oracle_step(sd0, 5, xs, ws, drops, device=DEV)
+    noise = fp32_noise(sd0, (x,), g64, step=lambda dev, perm: oracle_step(
+        sd0, 5, xs, ws, drops, torch.float32, dev, perms=None if perm is None else [perm]))
+    got = {"y": yg.detach(), "dx": xg.grad}
+    got.update({k: v.grad for k, v in m.named_parameters() if v.grad is not None})
+    assert "prelu.weight" in g64 and set(g64) == set(got)
+    check_ratios(noise_ratios(got, g64, noise), "3DPW step, do_in p = 0.3")
 
 
 # ---- engine: loss and test metric ----------------------------------------------
