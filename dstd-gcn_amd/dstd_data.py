@@ -20,7 +20,10 @@ in one pass over one loader (include/ext/dstd_gcn_eval.h).
 and shift of every joint, uniform noise on the observed frames -- that the
 gather applies in its one launch (include/ext/dstd_gcn_augment.h):
 ``DeviceLoader(..., augment=Augment(...))``, or ``gather(index, transform=,
-noise=, noise_seed=)`` for a caller's own transforms.
+noise=, noise_seed=)`` for a caller's own transforms.  ``Augment(speed=)`` /
+``gather(rate=)`` also play every window faster or slower, resampled in time in
+that same launch from the frames a set built by ``from_sequences`` holds after
+the window (include/ext/dstd_gcn_warp.h; ``room``, ``fit_rate``).
 
 There is no CPU gather: a set built with ``device="cpu"`` serves the host-side
 bookkeeping (weights, window starts, index order) only.
@@ -191,6 +194,17 @@ def _check_augmentation(seqs, index, transform, noise, noise_seed):
     return noise, int(noise_seed) % 2 ** 64
 
 
+def _check_rate(seqs, index, rate):
+    """The ``rate`` argument of DeviceSequences.gather, checked before anything
+    else (no device needed)."""
+    if not isinstance(index, torch.Tensor):
+        raise ValueError("index: a contiguous int64 vector on the set's device")
+    B = index.numel()
+    if (not isinstance(rate, torch.Tensor) or rate.dtype != torch.float32 or tuple(rate.shape) != (B,)
+            or not rate.is_contiguous() or rate.device != seqs._frames.device):
+        raise ValueError(f"rate: a contiguous float32 [{B}] tensor on {seqs._frames.device}, got {_describe(rate)}")
+
+
 def _describe(t):
     if not isinstance(t, torch.Tensor):
         return type(t).__name__
@@ -208,9 +222,14 @@ class Augment:
     a uniformly distributed rotation.  ``scale``: ``(lo, hi)``, uniform, ``0 <
     lo <= hi``.  ``shift``: an amplitude; each component of ``t`` is uniform in
     ``[-shift, shift]``.  ``noise``: the jitter's amplitude (not drawn here:
-    the gather derives it from a seed, the window and the frame)."""
+    the gather derives it from a seed, the window and the frame).
 
-    def __init__(self, rotate=None, scale=None, shift=None, noise=0.0):
+    ``speed``: ``(lo, hi)``, ``0 < lo <= hi`` -- a playback rate per sample,
+    uniform in ``[lo, hi]``, at which the gather resamples the window in time
+    (include/ext/dstd_gcn_warp.h).  Drawn by ``draw_speed``, from a generator
+    of its own: ``draw`` does not know of it."""
+
+    def __init__(self, rotate=None, scale=None, shift=None, noise=0.0, speed=None):
         if rotate is not None and rotate != "so3":
             try:
                 axis, max_angle = rotate
@@ -236,7 +255,27 @@ class Augment:
         noise = float(noise)
         if not 0.0 <= noise <= _FP32_MAX:
             raise ValueError(f"noise: a non-negative finite (fp32) amplitude, got {noise!r}")
-        self.rotate, self.scale, self.shift, self.noise = rotate, scale, shift, noise
+        if speed is not None:
+            try:
+                lo, hi = (float(v) for v in speed)
+                ok = 0.0 < lo <= hi < float("inf")
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"speed: (lo, hi) with 0 < lo <= hi, got {speed!r}")
+            speed = (lo, hi)
+        self.rotate, self.scale, self.shift, self.noise, self.speed = rotate, scale, shift, noise, speed
+
+    def draw_speed(self, B, generator, device):
+        """One playback rate per sample: fp32 ``[B]`` on ``device``, uniform in
+        ``[lo, hi]`` and clamped to it as ``scale`` is, or None without
+        ``speed``.  One torch.rand on ``device`` fed from ``generator``; no host
+        synchronisation."""
+        if self.speed is None:
+            return None
+        lo, hi = self.speed
+        u = torch.rand(B, generator=generator, device=torch.device(device), dtype=torch.float32)
+        return (lo + (hi - lo) * u).clamp_(lo, hi)
 
     def draw(self, B, generator, device):
         """One ``[A | t]`` per sample: fp32 ``[B, 12]`` on ``device``, or None
@@ -299,7 +338,7 @@ class DeviceSequences:
     it ``groups`` is None and the set counts as one group named "all"."""
 
     def __init__(self, frames, starts, seq_len, dim_used, input_n, output_n, padding, device, mirror_src=None,
-                 scale_tsfm=None, joint_weights=None, groups=None, group_names=None):
+                 scale_tsfm=None, joint_weights=None, groups=None, group_names=None, room=None):
         frames = np.asarray(frames, dtype=np.float64)
         starts = np.asarray(starts, dtype=np.int64)
         if frames.ndim != 2 or frames.shape[0] < 1 or frames.shape[1] % 3 != 0:
@@ -345,6 +384,16 @@ class DeviceSequences:
             table, self.group_names = group_table(groups, self.n_windows, mirror_src is not None, group_names)
             self.groups = torch.from_numpy(table).to(dev)
         self.n_groups = len(self.group_names)
+        self.room, self._room = None, None
+        if room is not None:
+            r = np.asarray(room)
+            if r.ndim != 1 or len(r) != len(starts) or r.dtype.kind not in "iu":
+                raise ValueError(f"room: one int per stored window ({len(starts)}), got {r.dtype} {r.shape}")
+            r = r.astype(np.int64)
+            if r.min() < T - 1 or (starts + r).max() > F - 1 or r.max() >= 2 ** 31:
+                raise ValueError(f"room: {T - 1} <= room[n] and starts[n] + room[n] <= {F - 1} for every window")
+            self.room = r.astype(np.int32)
+            self._room = torch.from_numpy(self.room).to(dev)
         self._store = native.SeqStore(
             frames=self._frames.data_ptr(), used=self._used.data_ptr() if self._used is not None else None,
             starts=self._starts.data_ptr(), F=F, N=self.n_windows, T=T, D=D, Du=len(dim_used),
@@ -410,6 +459,8 @@ class DeviceSequences:
             groups = np.concatenate((groups, groups)) if groups is not None else None
         offsets = np.concatenate([[0], np.cumsum([len(s) for s in seqs])])
         starts = np.concatenate([off + np.arange(len(s) - T + 1) for off, s in zip(offsets, seqs)])
+        # a window's room: the frames of its own sequence from its start on (what a faster playback may read)
+        room = np.concatenate([len(s) - 1 - np.arange(len(s) - T + 1) for s in seqs])
         if groups is not None:
             groups = np.repeat(groups, [len(s) - T + 1 for s in seqs])
         # mean |x[t+1] - x[t]| over every window: pair p of a sequence lies in
@@ -425,7 +476,7 @@ class DeviceSequences:
         if scaler is not None:
             mirror_src = None
         return cls(np.concatenate(seqs, axis=0), starts, T, dim_used, input_n, output_n, padding, device, mirror_src,
-                   _as_scaler(scaler), _normalised_weights(motion, dim_used), groups, group_names)
+                   _as_scaler(scaler), _normalised_weights(motion, dim_used), groups, group_names, room=room)
 
     @classmethod
     def from_dataset(cls, ds, input_n, output_n, padding=True, device="cuda"):
@@ -477,15 +528,37 @@ class DeviceSequences:
     def nbytes(self):
         """Device memory the set holds."""
         held = (self._frames, self._used, self._starts, self._dim_used, self._frame_in, self._frame_inv,
-                self._mirror_src, self.groups)
+                self._mirror_src, self.groups, self._room)
         return sum(t.numel() * t.element_size() for t in held if t is not None)
 
     @property
     def starts(self):
         return self._starts
 
+    def fit_rate(self, index, rate):
+        """``rate`` (fp32 [B] on the set's device) capped per sample so that
+        the last frame of the warped window still lies in the window's room:
+        ``min(rate, room[w] / (T - 1))``, w the index folded over the mirrored
+        half; the cap is 1 on a set without a room table.  Indices outside the
+        set keep their rate (the gather skips those rows).  Torch ops on the
+        device, no host synchronisation.  The gather itself never reads past
+        the room -- a position beyond it shows the last frame in room -- so
+        this is what keeps an augmented window from freezing at the end of its
+        recording, not what keeps the reads in bounds."""
+        n = self.n_windows
+        w = torch.where(index >= n, index - n, index) if self._mirror_src is not None else index
+        ok = (w >= 0) & (w < n)
+        if self._room is None:
+            return torch.where(ok, rate.clamp(max=1.0), rate)
+        # the quotient rounded DOWN to fp32 (fp64 holds it to well below an fp32 ulp), so that
+        # cap * (T - 1) <= room exactly and the kernel's fp32 product cannot round past the room
+        exact = self._room[w.clamp(0, n - 1)].to(torch.float64) / float(max(self.seq_len - 1, 1))
+        cap = exact.to(torch.float32)
+        cap = torch.where(cap.to(torch.float64) > exact, torch.nextafter(cap, torch.zeros_like(cap)), cap)
+        return torch.where(ok, torch.minimum(rate, cap), rate)
+
     def gather(self, index, outputs=("inputs", "inputs_inv", "targets", "all_seqs"), out=None, transform=None,
-               noise=0.0, noise_seed=0):
+               noise=0.0, noise_seed=0, rate=None):
         """(inputs, inputs_inv, targets, all_seqs) of the windows ``index``
         (int64 device tensor [B]) by one dstd_batch_gather on the current
         stream; a name missing from ``outputs`` is not produced (None).
@@ -497,7 +570,18 @@ class DeviceSequences:
         ``inputs`` / ``inputs_inv`` alone, keyed by ``noise_seed``, the window
         and the source frame) augment the batch in the same single launch
         (dstd_batch_gather_aug, include/ext/dstd_gcn_augment.h).  A scaled set
-        takes noise, in the scaler's units, but no transform."""
+        takes noise, in the scaler's units, but no transform.
+
+        ``rate`` (contiguous fp32 [B] on the set's device: a playback speed per
+        sample) resamples every window in time, again in the same launch
+        (dstd_batch_gather_warp, include/ext/dstd_gcn_warp.h): window frame f
+        shows the recording at f * rate frames past the window's start,
+        blended linearly from the two stored frames around it, and all four
+        tensors are views of that warped window.  A window reads no further
+        than its room (``room``; ``fit_rate`` caps a rate to it).  A scaled
+        set takes a rate."""
+        if rate is not None:
+            _check_rate(self, index, rate)
         noise, noise_seed = _check_augmentation(self, index, transform, noise, noise_seed)
         if self.device.type != "cuda":
             raise RuntimeError(f"DeviceSequences.gather runs on the MI355X only (the set is on {self.device}); "
@@ -516,7 +600,14 @@ class DeviceSequences:
                 raise ValueError(f"{n}: expected {shapes[n]}, got {tuple(t.shape)}")
             res[n] = t
         p = {n: native.ptr(t, n) for n, t in res.items()}
-        if transform is None and noise == 0.0:
+        if rate is not None:
+            code = native.lib().dstd_batch_gather_warp(
+                native.ext_warp.seq_store_ref(self._store), self._room.data_ptr() if self._room is not None else None,
+                index.data_ptr(), B, rate.data_ptr(), transform.data_ptr() if transform is not None else None, noise,
+                noise_seed, p.get("inputs"), p.get("inputs_inv"), p.get("targets"), p.get("all_seqs"),
+                native.stream_handle(self._frames.device))
+            native.check(code, "dstd_batch_gather_warp")
+        elif transform is None and noise == 0.0:
             code = native.lib().dstd_batch_gather(ctypes.byref(self._store), index.data_ptr(), B, p.get("inputs"),
                                                   p.get("inputs_inv"), p.get("targets"), p.get("all_seqs"),
                                                   native.stream_handle(self._frames.device))
@@ -543,7 +634,17 @@ class DeviceLoader:
     + epoch`` when an epoch starts, so the order of windows is the same with
     and without augmentation; batch ``i`` of an epoch uses the noise seed
     ``noise_seed(seed, epoch, i)``.  ``last_transform`` and ``last_noise_seed``
-    describe the batch just yielded (None without ``augment``)."""
+    describe the batch just yielded (None without ``augment``).
+
+    With ``Augment(speed=...)`` every batch is also resampled in time: the
+    rates come from a third generator of their own, seeded ``rate_seed(seed,
+    epoch)`` when an epoch starts -- ``seed + epoch`` under a fixed tag, so that
+    its stream is not the transform generator's: from the same seed a rate and
+    a rotation angle would be drawn from the same uniform -- once per batch,
+    and capped by the set's ``fit_rate``.  The order of windows, the transforms
+    and the noise seeds are the same with and without ``speed``.  ``last_rate``
+    is the capped rate tensor of the batch just yielded (None without
+    ``speed``)."""
 
     def __init__(self, seqs, batch_size, shuffle=False, drop_last=False, seed=0, augment=None):
         if batch_size < 1:
@@ -557,8 +658,8 @@ class DeviceLoader:
         if augment is not None and not isinstance(augment, Augment):
             raise TypeError(f"augment: an Augment or None, got {type(augment).__name__}")
         self.augment = augment
-        self.last_transform = self.last_noise_seed = None
-        self._aug_generator = None
+        self.last_transform = self.last_noise_seed = self.last_rate = None
+        self._aug_generator = self._rate_generator = None
 
     def __len__(self):
         n = len(self.seqs)
@@ -585,6 +686,17 @@ class DeviceLoader:
         """The noise seed of batch ``i`` of epoch ``epoch`` (Python ints)."""
         return (((int(seed) + int(epoch)) << 32) ^ int(i)) % 2 ** 64
 
+    RATE_STREAM = 0x9E3779B97F4A7C15  # tag of the rate generator's seed
+
+    @classmethod
+    def rate_seed(cls, seed, epoch):
+        """The seed of the rate generator of epoch ``epoch`` (Python ints):
+        ``seed + epoch`` with a fixed tag xor-ed in.  The transform generator is
+        seeded ``seed + epoch`` itself and its first draw can be one
+        ``rand(B)``, as a rate draw is: from the same seed every sample's rate
+        would be a function of its rotation angle."""
+        return ((int(seed) + int(epoch)) ^ cls.RATE_STREAM) % 2 ** 64
+
     def __iter__(self):
         aug = self.augment
         if aug is None:
@@ -596,12 +708,19 @@ class DeviceLoader:
         if self._aug_generator is None:
             self._aug_generator = torch.Generator(device=dev)
         self._aug_generator.manual_seed(self.seed + epoch)
+        if aug.speed is not None:
+            if self._rate_generator is None:
+                self._rate_generator = torch.Generator(device=dev)
+            self._rate_generator.manual_seed(self.rate_seed(self.seed, epoch))
         for i, idx in enumerate(self.index_batches()):
             self.last_index = idx
             self.last_transform = aug.draw(idx.numel(), self._aug_generator, dev)
             self.last_noise_seed = self.noise_seed(self.seed, epoch, i)
+            self.last_rate = None
+            if aug.speed is not None:
+                self.last_rate = self.seqs.fit_rate(idx, aug.draw_speed(idx.numel(), self._rate_generator, dev))
             yield self.seqs.gather(idx, transform=self.last_transform, noise=aug.noise,
-                                   noise_seed=self.last_noise_seed)
+                                   noise_seed=self.last_noise_seed, rate=self.last_rate)
 
 
 __all__ = ["Augment", "DeviceSequences", "DeviceLoader", "MeanStd", "frame_maps", "group_table", "mirror_source"]

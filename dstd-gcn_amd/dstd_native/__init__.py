@@ -1,5 +1,5 @@
 """ctypes binding of the MI355X C ABI (include/*.h, declared in abi.py; include/ext/*.h in ext.py,
-ext_eval.py, ext_augment.py, ext_stride.py and ext_stride_train.py).
+ext_eval.py, ext_augment.py, ext_stride.py, ext_stride_train.py and ext_warp.py).
 
 The shared library ``libdstd_gcn.so`` is built in-tree (``make -C dstd-gcn_amd``
 or ``__graft_entry__.build()``).  There is no fallback: if the library is
@@ -16,6 +16,7 @@ from . import ext_eval  # include/ext/dstd_gcn_eval.h: likewise (ext.ALL and ext
 from . import ext_augment  # include/ext/dstd_gcn_augment.h: likewise
 from . import ext_stride  # include/ext/dstd_gcn_stride.h: likewise
 from . import ext_stride_train  # include/ext/dstd_gcn_stride_train.h: likewise
+from . import ext_warp  # include/ext/dstd_gcn_warp.h: likewise
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DSTD_LIB overrides the library (A/B experiments with variant builds)
@@ -68,7 +69,7 @@ def lib():
         # library built from an earlier revision on purpose
         foreign = os.environ.get("DSTD_AB_FOREIGN_LIB") == "1"
         declare(L, allow_missing=foreign, extra={**ext.ALL, **ext_eval.ABI, **ext_augment.ABI, **ext_stride.ABI,
-                                                       **ext_stride_train.ABI})
+                                                       **ext_stride_train.ABI, **ext_warp.ABI})
         built, tree = L.dstd_source_hash().decode(), source_hash()
         if tree is not None and built != tree and not foreign:
             raise RuntimeError(f"{LIB_PATH} was built from other sources (hash {built}, this tree {tree}): "
