@@ -4,8 +4,9 @@
 // the chain's backward -- K dstd_model_train_bwd_ex around a gradient history
 // Gh of the known sequence, with scheduled sampling at the window boundaries.
 //
-// Window 0 is csrc/dstd_window.h's k_window_obs; the glue kernels are this
-// file's, written as that header's are: destination-driven, a wave owns one row
+// The forward is dstd_rollout.hip's chain_fwd (dstd_chain.h) with adv = S; the
+// backward glue kernels are this file's, written as csrc/dstd_window.h's are:
+// destination-driven, a wave owns one row
 // and its lanes walk the row's V * 3 floats, plain dword accesses, 64-bit
 // element offsets, no LDS, no atomics, wave-uniform row arithmetic.  A sample's
 // mask byte is read once per row into a scalar, so the row's branch is
@@ -15,7 +16,7 @@
 #include "dstd_common.h"
 #include "dstd_host.h"
 #pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // k_window_roll, the unstrided chain's glue, is not used here
+#pragma clang diagnostic ignored "-Wunused-function"  // the window kernels are chain_fwd's, not used here
 #include "dstd_window.h"
 #pragma clang diagnostic pop
 #include "dstd_chain.h"
@@ -23,56 +24,6 @@
 using namespace dstd;
 
 namespace {
-
-// After window k (f0 = k * S), row (b, s) of the window:
-//   emit   out[b][f0 + s - Tin] = y[b][s]        for Tin <= s < Tin + S while f0 + s - Tin < H
-//   build  xn[b][s]             = seq[b][S + min(s, Tin - 1)],  seq = x below Tin, y from Tin on
-// xn == nullptr (after the last forward): the emit alone.  xn is window k + 1's
-// own saved slot.  For a free-running sample seq[S + i] is h[f0 + S + i], the
-// frame dstd_predict_stride.hip's k_stride_glue takes from obs, out or y: every
-// row of x below Tin is a copy of that frame, so the two build the same window.
-// A sample that mrow (row k + 1 of the mask; nullptr: none) forces takes its
-// rows from truth instead -- frame tb[h] + ts[h] * min(s, Tin - 1) of sample
-// b mod Bt, h = b / Bt, where tb[h] is the half's truth frame of the window's
-// first row (checked on the host to lie in 0 .. truth_T - 1 for every row) --
-// and hands them on through x like any observed frame.
-//
-// No hazard: the launch reads x, y and truth and writes out and xn, which are
-// five different buffers; S + min(s, Tin - 1) <= S + Tin - 1 <= T - 1.
-__global__ __launch_bounds__(DSTD_THREADS) void k_stride_train_glue(const float* x, const float* y, float* out,
-                                                                    float* xn, const float* truth,
-                                                                    const unsigned char* mrow, int B, int Bt, int T,
-                                                                    int Tin, int R, int H, int S, int f0, int truth_T,
-                                                                    int tb0, int ts0, int tb1, int ts1) {
-  const int lane = threadIdx.x & (DSTD_WAVE - 1);
-  const long long rows = (long long)B * T;
-  const long long stride = (long long)gridDim.x * DSTD_WAVES;
-  for (long long r = (long long)blockIdx.x * DSTD_WAVES + (threadIdx.x >> 6); r < rows; r += stride) {
-    const long long b = r / T;
-    const int s = (int)(r - b * T);
-    const int f = f0 + s - Tin;
-    if (s >= Tin && s < Tin + S && f < H) {
-      const float* src = y + r * R;
-      float* dst = out + (b * H + f) * R;
-      for (int d = lane; d < R; d += DSTD_WAVE) dst[d] = src[d];
-    }
-    if (xn) {
-      const int ms = s < Tin ? s : Tin - 1;
-      const float* src;
-      if (mrow && __builtin_amdgcn_readfirstlane((int)mrow[b])) {
-        const bool second = b >= Bt;
-        const long long bt = second ? b - Bt : b;
-        const int frame = second ? tb1 + ts1 * ms : tb0 + ts0 * ms;
-        src = truth + (bt * truth_T + frame) * R;
-      } else {
-        const int t = S + ms;  // S <= t <= T - 1
-        src = (t < Tin ? x : y) + (b * T + t) * R;
-      }
-      float* dst = xn + r * R;
-      for (int d = lane; d < R; d += DSTD_WAVE) dst[d] = src[d];
-    }
-  }
-}
 
 // Gh = +0.  Rows: B * (Tin + H).
 __global__ __launch_bounds__(DSTD_THREADS) void k_stride_bwd_zero(float* Gh, long long rows, int R) {
@@ -146,87 +97,29 @@ inline size_t gh_bytes(int B, int V, int Tin, int H) {
   return rup256((size_t)B * (size_t)(frames > 0 ? frames : 0) * V * 3 * sizeof(float));
 }
 
-// The arguments every entry point checks alike, before the model's own: K on success.
-int chain_args(int T, int Tin, int horizon, int S, float dropout_p, const unsigned long long* seeds, long long* K) {
-  if (Tin < 1 || Tin >= T || horizon < 1) return DSTD_EINVAL;
-  if (S < 1 || S > T - Tin) return DSTD_EINVAL;
-  if (dropout_p > 0.f && !seeds) return DSTD_EINVAL;
-  *K = ((long long)horizon + S - 1) / S;
-  return DSTD_OK;
-}
-
-int strided_fwd(const dstd_model_params* p, const float* obs, int B, int input_n, int horizon, int stride,
-                float momentum, float dropout_p, const unsigned long long* seeds, float* out, void* saved,
-                size_t saved_bytes, const float* truth, int truth_T, const int* t0, const int* step,
-                const unsigned char* mask, void* stream, unsigned flags) {
-  StreamDeviceGuard dev_guard_(stream, obs);
-  if (!p || !obs || !out || !saved) return DSTD_EINVAL;
-  const int T = p->T, V = p->V, C = p->num_feature, L_ = p->num_layers, Tin = input_n, S = stride;
-  long long Kll = 0;
-  if (const int e = chain_args(T, Tin, horizon, S, dropout_p, seeds, &Kll)) return e;
-  const int probe = dstd_model_train_fwd_ex(p, obs, B, momentum, dropout_p, seed_of(seeds, 0, flags), out, saved, 0,
-                                            stream, flags);
-  if (probe == DSTD_EINVAL) return DSTD_EINVAL;
-  Teacher tf;
-  if (const int e = teacher_check(truth, truth_T, t0, step, mask, flags, Tin, S, Kll, &tf)) return e;
-  if (const int e = chain_code(probe, Kll)) return e;
-  const int K = (int)Kll;
-  if (saved_bytes < dstd_model_rollout_saved_bytes(B, T, V, C, L_, K)) return DSTD_EWORKSPACE;
-
-  const size_t W = window_bytes(B, T, V), SV = model_saved(B, T, V, C, L_);
-  char* base = (char*)saved;
-  float* y = (float*)base;
-  auto xk = [&](int k) { return (float*)(base + W + (size_t)k * (W + SV)); };
-  auto sk = [&](int k) { return (void*)(base + W + (size_t)k * (W + SV) + W); };
-
-  hipStream_t s = (hipStream_t)stream;
-  const int R = V * 3, grid = row_grid(B, T);
-  const int Bt = (flags & DSTD_TRAIN_PAIRED) ? B / 2 : B;
-  k_window_obs<<<grid, DSTD_THREADS, 0, s>>>(obs, xk(0), B, T, Tin, R);
-  DSTD_TRY(hipGetLastError());
-  for (int k = 0; k < K; ++k) {
-    if (const int e = dstd_model_train_fwd_ex(p, xk(k), B, momentum, dropout_p, seed_of(seeds, k, flags), y, sk(k), SV,
-                                              stream, flags))
-      return e;
-    const bool next = k + 1 < K;
-    const unsigned char* mrow = next && tf.mask ? tf.mask + (size_t)(k + 1) * B : nullptr;
-    k_stride_train_glue<<<grid, DSTD_THREADS, 0, s>>>(xk(k), y, out, next ? xk(k + 1) : nullptr, tf.truth, mrow, B, Bt, T,
-                                                      Tin, R, horizon, S, k * S, tf.truth_T, tf.base(0, k + 1, S),
-                                                      tf.step[0], tf.base(1, k + 1, S), tf.step[1]);
-    DSTD_TRY(hipGetLastError());
-  }
-  return DSTD_OK;
-}
-
 // The backward of the chain: every window from K - 1 down to 0 (only < 0), or
 // window `only` alone, which finds Gh where the calls for the later windows
 // left it.
-int strided_bwd(const dstd_model_params* p, int B, int input_n, int horizon, int stride, int only, float dropout_p,
+int strided_bwd(const dstd_model_params* p, int B, int Tin, int horizon, int S, int only, float dropout_p,
                 const unsigned long long* seeds, const void* saved, size_t saved_bytes, const float* dout,
-                const dstd_model_grads* g, float* dobs, void* workspace, size_t workspace_bytes, const float* truth,
-                int truth_T, const int* t0, const int* step, const unsigned char* mask, void* stream,
-                unsigned flags) {
+                const dstd_model_grads* g, float* dobs, void* workspace, size_t workspace_bytes, const TeacherArgs& ta,
+                void* stream, unsigned flags) {
   StreamDeviceGuard dev_guard_(stream, dout);
   if (!p || !saved || !dout || !g || !workspace) return DSTD_EINVAL;
-  const int T = p->T, V = p->V, C = p->num_feature, L_ = p->num_layers, Tin = input_n, S = stride;
-  long long Kll = 0;
-  if (const int e = chain_args(T, Tin, horizon, S, dropout_p, seeds, &Kll)) return e;
-  const int probe = dstd_model_train_bwd_ex(p, (const float*)saved, B, dropout_p, seed_of(seeds, 0, flags), saved, 0,
-                                            dout, g, nullptr, workspace, 0, stream, flags);
-  if (probe == DSTD_EINVAL) return DSTD_EINVAL;
+  int K = 0;
   Teacher tf;
-  if (const int e = teacher_check(truth, truth_T, t0, step, mask, flags, Tin, S, Kll, &tf)) return e;
-  if (only >= Kll) return DSTD_EINVAL;
-  if (const int e = chain_code(probe, Kll)) return e;
-  const int K = (int)Kll;
-  if (saved_bytes < dstd_model_rollout_saved_bytes(B, T, V, C, L_, K)) return DSTD_EWORKSPACE;
+  auto probe = [&] {
+    return dstd_model_train_bwd_ex(p, (const float*)saved, B, dropout_p, seed_of(seeds, 0, flags), saved, 0, dout, g,
+                                   nullptr, workspace, 0, stream, flags);
+  };
+  if (const int e = chain_open(p, B, Tin, horizon, S, only, dropout_p, seeds, ta, flags, saved_bytes, probe, &K, &tf))
+    return e;
+  const int T = p->T, V = p->V, C = p->num_feature, L_ = p->num_layers;
   if (workspace_bytes < dstd_model_rollout_strided_workspace_bytes(B, T, V, C, L_, Tin, horizon))
     return DSTD_EWORKSPACE;
 
-  const size_t W = window_bytes(B, T, V), SV = model_saved(B, T, V, C, L_), M = model_ws(B, T, V, C, L_);
-  const char* base = (const char*)saved;
-  auto xk = [&](int k) { return (const float*)(base + W + (size_t)k * (W + SV)); };
-  auto sk = [&](int k) { return (const void*)(base + W + (size_t)k * (W + SV) + W); };
+  const ChainSaved at(saved, p, B);
+  const size_t W = at.W, M = model_ws(B, T, V, C, L_);
   char* wbase = (char*)workspace + M;
   float* dy = (float*)wbase;
   float* dx = (float*)(wbase + W);
@@ -245,11 +138,11 @@ int strided_bwd(const dstd_model_params* p, int B, int input_n, int horizon, int
     k_stride_bwd_dy<<<grid, DSTD_THREADS, 0, s>>>(dout, Gh, dy, B, T, Tin, R, horizon, S, k * S);
     DSTD_TRY(hipGetLastError());
     const bool need_dx = k > 0 || dobs;  // window 0's input gradient only for dobs
-    if (const int e = dstd_model_train_bwd_ex(p, xk(k), B, dropout_p, seed_of(seeds, k, flags), sk(k), SV, dy, g,
-                                              need_dx ? dx : nullptr, workspace, M, stream, flags))
+    if (const int e = dstd_model_train_bwd_ex(p, at.x(k), B, dropout_p, seed_of(seeds, k, flags), at.saved(k), at.S, dy,
+                                              g, need_dx ? dx : nullptr, workspace, M, stream, flags))
       return e;
     if (need_dx) {
-      const unsigned char* mrow = k > 0 && tf.mask ? tf.mask + (size_t)k * B : nullptr;
+      const unsigned char* mrow = k > 0 ? tf.row(k, B) : nullptr;
       k_stride_bwd_acc<<<row_grid(B, Tin), DSTD_THREADS, 0, s>>>(dx, Gh, k == 0 ? dobs : nullptr, mrow, B, T, Tin, R,
                                                                  horizon, k * S);
       DSTD_TRY(hipGetLastError());
@@ -272,8 +165,8 @@ int dstd_model_rollout_strided_fwd(const dstd_model_params* p, const float* obs,
                                    float* out, void* saved, size_t saved_bytes, const float* truth, int truth_T,
                                    const int* t0, const int* step, const unsigned char* mask, void* stream,
                                    unsigned flags) {
-  return strided_fwd(p, obs, B, input_n, horizon, stride, momentum, dropout_p, seeds, out, saved, saved_bytes, truth,
-                     truth_T, t0, step, mask, stream, flags);
+  return chain_fwd(p, obs, B, input_n, horizon, stride, momentum, dropout_p, seeds, out, saved, saved_bytes,
+                   {truth, truth_T, t0, step, mask}, stream, flags);
 }
 
 int dstd_model_rollout_strided_bwd(const dstd_model_params* p, int B, int input_n, int horizon, int stride,
@@ -283,7 +176,7 @@ int dstd_model_rollout_strided_bwd(const dstd_model_params* p, int B, int input_
                                    const int* t0, const int* step, const unsigned char* mask, void* stream,
                                    unsigned flags) {
   return strided_bwd(p, B, input_n, horizon, stride, -1, dropout_p, seeds, saved, saved_bytes, dout, g, dobs,
-                     workspace, workspace_bytes, truth, truth_T, t0, step, mask, stream, flags);
+                     workspace, workspace_bytes, {truth, truth_T, t0, step, mask}, stream, flags);
 }
 
 int dstd_model_rollout_strided_bwd_window(const dstd_model_params* p, int B, int input_n, int horizon, int stride,
@@ -294,7 +187,7 @@ int dstd_model_rollout_strided_bwd_window(const dstd_model_params* p, int B, int
                                           void* stream, unsigned flags) {
   if (k < 0) return DSTD_EINVAL;
   return strided_bwd(p, B, input_n, horizon, stride, k, dropout_p, seeds, saved, saved_bytes, dout, g, dobs, workspace,
-                     workspace_bytes, truth, truth_T, t0, step, mask, stream, flags);
+                     workspace_bytes, {truth, truth_T, t0, step, mask}, stream, flags);
 }
 
 int dstd_model_rollout_strided_glue_bwd(int step, const float* dout, const float* dx, float* Gh, float* dst,

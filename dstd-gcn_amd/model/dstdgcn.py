@@ -29,6 +29,7 @@ the native training path with BatchNorm on its running statistics
 back-propagates through its eval-mode modules; under torch.no_grad() (or
 with frozen parameters and input) eval runs the fused inference kernels.
 """
+import collections
 import itertools
 import numbers
 import operator
@@ -572,20 +573,44 @@ def _param_hooks(params):
     return any(p._backward_hooks or getattr(p, "_post_accumulate_grad_hooks", None) for p in params)
 
 
-class _RolloutTrain(torch.autograd.Function):
+# The three families of chain entry points (include/ext/dstd_gcn_rollout.h,
+# dstd_gcn_teacher.h, dstd_gcn_stride_train.h), keyed by (stride is None,
+# mask is None): the stem of _fwd / _bwd / _bwd_window, whether ``stride``
+# follows ``horizon`` in their arguments (and the workspace is the strided
+# one, sized by input_n and horizon too), and whether they take the teacher's
+# five arguments -- NULL in a free-running strided chain.
+_Chain = collections.namedtuple("_Chain", "stem strided teacher")
+_CHAINS = {(True, True): _Chain("dstd_model_rollout", False, False),
+           (True, False): _Chain("dstd_model_rollout_tf", False, True),
+           (False, True): _Chain("dstd_model_rollout_strided", True, True),
+           (False, False): _Chain("dstd_model_rollout_strided", True, True)}
+
+
+class _RolloutChain(torch.autograd.Function):
     """DSTDGCN.rollout under autograd: the whole chain of train forwards as one
     native call and its backward as another (include/ext/dstd_gcn_rollout.h).
     Built like _ModelTrain -- flags, device seeds, the anchored parameters and
     the in-place gradient arena -- but eager only: there is no custom op for
-    the chain, so both directions call the C ABI directly."""
+    the chain, so both directions call the C ABI directly.
+
+    One Function for every chain.  ``stride`` None: whole windows; else every
+    window hands on its first ``stride`` frames (a stride below
+    ``output_time_frame``: include/ext/dstd_gcn_stride_train.h), and the chain
+    has ``ceil(horizon / stride)`` windows.  ``mask`` None: free running
+    (``teacher`` and ``maps`` are None too); else scheduled sampling
+    (include/ext/dstd_gcn_teacher.h) with the teacher's frames, one (t0, step)
+    frame map per half and the mask, which stays in ctx, since the backward
+    reads it again; the teacher and the mask get no gradient.  Which entry
+    points that makes, and how their arguments differ, is _CHAINS'."""
 
     @staticmethod
-    def forward(ctx, model, paired, horizon, obs, *params):
+    def forward(ctx, model, paired, horizon, stride, obs, teacher, mask, maps, *params):
         L = native.lib()
         n, tin, v, c = obs.shape
         dev = obs.device
         t = tin + model.output_time_frame
-        windows = -(-horizon // model.output_time_frame)
+        windows = -(-horizon // (stride or model.output_time_frame))
+        chain = ctx.chain = _CHAINS[stride is None, mask is None]
         flags = _bn_flags(model) | (native.TRAIN_PAIRED if paired else 0)
         if getattr(model, "_dstd_one_stream", False):
             flags |= native.TRAIN_ONE_STREAM
@@ -601,16 +626,25 @@ class _RolloutTrain(torch.autograd.Function):
         out = obs.new_empty(n, horizon, v, c)
         nbytes = L.dstd_model_rollout_saved_bytes(n, t, v, model.num_feature, model.num_layers, windows)
         saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        code = L.dstd_model_rollout_fwd(native.ext.model_params_ref(model._native_params()), native.ptr(obs, "observed"),
-                                        n, tin, horizon, _bn_momentum(model), drop, seeds, native.ptr(out, "out"),
-                                        saved.data_ptr(), nbytes, native.stream_handle(dev), flags)
-        native.check(code, "dstd_model_rollout_fwd")
+        ctx.mask = mask  # the backward reads it again
+        ctx.tf = ()
+        if mask is not None:
+            ctx.tf = (native.ptr(teacher, "teacher"), teacher.shape[1], *native.ext.frame_maps(maps), mask.data_ptr())
+        elif chain.teacher:
+            ctx.tf = (None, 0, None, None, None)
+        # (horizon[, stride]) as every entry point of the family takes them
+        ctx.span = (horizon, stride) if chain.strided else (horizon,)
+        code = getattr(L, chain.stem + "_fwd")(native.ext.model_params_ref(model._native_params()),
+                                               native.ptr(obs, "observed"), n, tin, *ctx.span, _bn_momentum(model),
+                                               drop, seeds, native.ptr(out, "out"), saved.data_ptr(), nbytes, *ctx.tf,
+                                               native.stream_handle(dev), flags)
+        native.check(code, chain.stem + "_fwd")
         if not flags & native.TRAIN_RUNNING_STATS:
             # the running statistics were updated once per window (twice when paired)
             torch.autograd.graph.increment_version(buffers)
             _count_batch(model, windows * (2 if paired else 1))
         ctx.model, ctx.saved_buf, ctx.drop, ctx.flags, ctx.shape = model, saved, drop, flags, (n, tin, v, c)
-        ctx.horizon = horizon
+        ctx.horizon, ctx.windows = horizon, windows
         ctx.anchored = len(params) == 1 and params[0] is getattr(model, "_dstd_anchor_t", None)
         ctx.params = params_all if ctx.anchored else list(params)
         return out
@@ -618,264 +652,7 @@ class _RolloutTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         L = native.lib()
-        model = ctx.model
-        n, tin, v, c = ctx.shape
-        dev = dout.device
-        dout = dout.contiguous()
-        need_dx = bool(ctx.needs_input_grad[3])
-        if ctx.saved_buf is None:
-            raise RuntimeError("DSTDGCN.rollout: backward through the chain a second time "
-                               "(its saved windows were freed by the first)")
-        arena, direct = None, False
-        if ctx.anchored or (getattr(model, "_dstd_inplace_grads", False) and not _param_hooks(ctx.params)):
-            arena, direct = native.grad_sink(model, ctx.params, dev)
-        t = tin + model.output_time_frame
-        windows = -(-ctx.horizon // model.output_time_frame)
-        ws = native.workspace(dev, L.dstd_model_rollout_workspace_bytes(n, t, v, model.num_feature, model.num_layers))
-        dobs = dout.new_empty(n, tin, v, c) if need_dx else None
-        pref = native.ext.model_params_ref(model._native_params())
-        tail = (ctx.drop, ctx.seed_t.data_ptr() if ctx.seed_t is not None else None, ctx.saved_buf.data_ptr(),
-                ctx.saved_buf.numel(), native.ptr(dout, "dout"))
-        tail2 = (dobs.data_ptr() if need_dx else None, ws.data_ptr(), ws.numel(), native.stream_handle(dev), ctx.flags)
-        if direct:
-            # every window accumulates (+=) into the parameters' .grad, as the K
-            # backwards of a loop do in this mode: one native call
-            g = getattr(arena, "model_grads", None)
-            if g is None:
-                g = arena.model_grads = model._native_grads(arena)
-            code = L.dstd_model_rollout_bwd(pref, n, tin, ctx.horizon, *tail, native.ext.model_grads_ref(g), *tail2)
-            native.check(code, "dstd_model_rollout_bwd")
-        else:
-            # gradients for autograd: a zeroed arena per window, summed in backward
-            # order (window K-1 first) -- what autograd makes of the K backwards of
-            # a loop, each of which returns an arena of its own.  One (+=) chain
-            # into a single arena would round alpha_sm, which both spatial
-            # operators of a block add into, differently from that.
-            numel = native.arena_numel(ctx.params)
-            bufs = torch.zeros(windows, numel, dtype=torch.float32, device=dev)
-            for k in range(windows - 1, -1, -1):
-                g = model._native_grads(native.GradArena(ctx.params, dev, buf=bufs[k]))
-                code = L.dstd_model_rollout_bwd_window(pref, n, tin, ctx.horizon, k, *tail,
-                                                       native.ext.model_grads_ref(g), *tail2)
-                native.check(code, "dstd_model_rollout_bwd_window")
-            total = bufs[windows - 1]
-            for k in range(windows - 2, -1, -1):
-                total += bufs[k]
-            arena = native.GradArena(ctx.params, dev, buf=total)
-        ctx.saved_buf = ctx.seed_t = None
-        if direct:
-            return (None, None, None, dobs, *([None] * (1 if ctx.anchored else len(arena.params))))
-        if ctx.anchored:
-            # .grad was set by someone else since the forward (_ModelTrain.backward)
-            for p, gv in zip(arena.params, arena.views()):
-                if gv is not None and p.requires_grad:
-                    if p.grad is None:
-                        p.grad = gv.clone()
-                    else:
-                        p.grad.add_(gv)
-            return (None, None, None, dobs, None)
-        return (None, None, None, dobs, *arena.views())
-
-
-class _RolloutTrainPair(torch.autograd.Function):
-    """DSTDGCN.rollout_pair's Function: _RolloutTrain over the concatenated
-    pair (DSTD_TRAIN_PAIRED) with the two halves as two outputs, as
-    _ModelTrainPair."""
-
-    @staticmethod
-    def forward(ctx, model, n, horizon, obs, *params):
-        out = _RolloutTrain.forward(ctx, model, True, horizon, obs, *params)
-        ctx.half = n
-        return out[:n], out[n:]
-
-    @staticmethod
-    def backward(ctx, d1, d2):
-        n2, tin, v, c = ctx.shape
-        n = ctx.half
-        ref = d1 if d1 is not None else d2
-        if d1 is None:
-            d1 = ref.new_zeros((n, ctx.horizon, v, c))
-        if d2 is None:
-            d2 = ref.new_zeros((n2 - n, ctx.horizon, v, c))
-        # (argument positions: model, n, horizon, obs, params -- as _RolloutTrain's model, paired, horizon, obs, params)
-        return _RolloutTrain.backward(ctx, torch.cat([d1, d2]))
-
-
-class _RolloutTeacher(torch.autograd.Function):
-    """_RolloutTrain with scheduled sampling (include/ext/dstd_gcn_teacher.h):
-    the same two native calls through the _tf_ entry points, which take the
-    teacher's frames, one (t0, step) frame map per half and the mask.  The mask
-    stays in ctx, since the backward reads it again; the teacher and the mask
-    get no gradient.  saved, workspace, arenas and what is returned to autograd
-    are _RolloutTrain's."""
-
-    @staticmethod
-    def forward(ctx, model, paired, horizon, obs, teacher, mask, maps, *params):
-        L = native.lib()
-        n, tin, v, c = obs.shape
-        dev = obs.device
-        t = tin + model.output_time_frame
-        windows = -(-horizon // model.output_time_frame)
-        flags = _bn_flags(model) | (native.TRAIN_PAIRED if paired else 0)
-        if getattr(model, "_dstd_one_stream", False):
-            flags |= native.TRAIN_ONE_STREAM
-        drop = float(model.do_in.p) if model.do_in.training else 0.0
-        seeds, ctx.seed_t = None, None
-        if drop > 0:
-            ctx.seed_t = torch.randint(0, 2 ** 62, (windows,), device=dev, dtype=torch.int64)
-            seeds = ctx.seed_t.data_ptr()
-            flags |= native.TRAIN_SEED_DEVICE
-        params_all, buffers = model._tree.get(model)
-        out = obs.new_empty(n, horizon, v, c)
-        nbytes = L.dstd_model_rollout_saved_bytes(n, t, v, model.num_feature, model.num_layers, windows)
-        saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ctx.mask = mask
-        ctx.tf = (native.ptr(teacher, "teacher"), teacher.shape[1], *native.ext.frame_maps(maps), mask.data_ptr())
-        code = L.dstd_model_rollout_tf_fwd(native.ext.model_params_ref(model._native_params()),
-                                           native.ptr(obs, "observed"), n, tin, horizon, _bn_momentum(model), drop,
-                                           seeds, native.ptr(out, "out"), saved.data_ptr(), nbytes, *ctx.tf,
-                                           native.stream_handle(dev), flags)
-        native.check(code, "dstd_model_rollout_tf_fwd")
-        if not flags & native.TRAIN_RUNNING_STATS:
-            torch.autograd.graph.increment_version(buffers)
-            _count_batch(model, windows * (2 if paired else 1))
-        ctx.model, ctx.saved_buf, ctx.drop, ctx.flags, ctx.shape = model, saved, drop, flags, (n, tin, v, c)
-        ctx.horizon = horizon
-        ctx.anchored = len(params) == 1 and params[0] is getattr(model, "_dstd_anchor_t", None)
-        ctx.params = params_all if ctx.anchored else list(params)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        L = native.lib()
-        model = ctx.model
-        n, tin, v, c = ctx.shape
-        dev = dout.device
-        dout = dout.contiguous()
-        need_dx = bool(ctx.needs_input_grad[3])
-        if ctx.saved_buf is None:
-            raise RuntimeError("DSTDGCN.rollout: backward through the chain a second time "
-                               "(its saved windows were freed by the first)")
-        arena, direct = None, False
-        if ctx.anchored or (getattr(model, "_dstd_inplace_grads", False) and not _param_hooks(ctx.params)):
-            arena, direct = native.grad_sink(model, ctx.params, dev)
-        t = tin + model.output_time_frame
-        windows = -(-ctx.horizon // model.output_time_frame)
-        ws = native.workspace(dev, L.dstd_model_rollout_workspace_bytes(n, t, v, model.num_feature, model.num_layers))
-        dobs = dout.new_empty(n, tin, v, c) if need_dx else None
-        pref = native.ext.model_params_ref(model._native_params())
-        tail = (ctx.drop, ctx.seed_t.data_ptr() if ctx.seed_t is not None else None, ctx.saved_buf.data_ptr(),
-                ctx.saved_buf.numel(), native.ptr(dout, "dout"))
-        tail2 = (dobs.data_ptr() if need_dx else None, ws.data_ptr(), ws.numel(), *ctx.tf, native.stream_handle(dev),
-                 ctx.flags)
-        if direct:  # one (+=) chain into the parameters' .grad
-            g = getattr(arena, "model_grads", None)
-            if g is None:
-                g = arena.model_grads = model._native_grads(arena)
-            code = L.dstd_model_rollout_tf_bwd(pref, n, tin, ctx.horizon, *tail, native.ext.model_grads_ref(g), *tail2)
-            native.check(code, "dstd_model_rollout_tf_bwd")
-        else:  # an arena per window, summed in backward order (_RolloutTrain.backward says why)
-            numel = native.arena_numel(ctx.params)
-            bufs = torch.zeros(windows, numel, dtype=torch.float32, device=dev)
-            for k in range(windows - 1, -1, -1):
-                g = model._native_grads(native.GradArena(ctx.params, dev, buf=bufs[k]))
-                code = L.dstd_model_rollout_tf_bwd_window(pref, n, tin, ctx.horizon, k, *tail,
-                                                          native.ext.model_grads_ref(g), *tail2)
-                native.check(code, "dstd_model_rollout_tf_bwd_window")
-            total = bufs[windows - 1]
-            for k in range(windows - 2, -1, -1):
-                total += bufs[k]
-            arena = native.GradArena(ctx.params, dev, buf=total)
-        ctx.saved_buf = ctx.seed_t = ctx.mask = ctx.tf = None
-        head = (None, None, None, dobs, None, None, None)  # model, paired, horizon, obs, teacher, mask, maps
-        if direct:
-            return (*head, *([None] * (1 if ctx.anchored else len(arena.params))))
-        if ctx.anchored:
-            for p, gv in zip(arena.params, arena.views()):
-                if gv is not None and p.requires_grad:
-                    if p.grad is None:
-                        p.grad = gv.clone()
-                    else:
-                        p.grad.add_(gv)
-            return (*head, None)
-        return (*head, *arena.views())
-
-
-class _RolloutTeacherPair(torch.autograd.Function):
-    """_RolloutTrainPair over _RolloutTeacher."""
-
-    @staticmethod
-    def forward(ctx, model, n, horizon, obs, teacher, mask, maps, *params):
-        out = _RolloutTeacher.forward(ctx, model, True, horizon, obs, teacher, mask, maps, *params)
-        ctx.half = n
-        return out[:n], out[n:]
-
-    @staticmethod
-    def backward(ctx, d1, d2):
-        n2, tin, v, c = ctx.shape
-        n = ctx.half
-        ref = d1 if d1 is not None else d2
-        if d1 is None:
-            d1 = ref.new_zeros((n, ctx.horizon, v, c))
-        if d2 is None:
-            d2 = ref.new_zeros((n2 - n, ctx.horizon, v, c))
-        return _RolloutTeacher.backward(ctx, torch.cat([d1, d2]))
-
-
-class _RolloutStrided(torch.autograd.Function):
-    """DSTDGCN.rollout with a stride below ``output_time_frame``
-    (include/ext/dstd_gcn_stride_train.h): every window hands on its first
-    ``stride`` frames, and the chain and its backward are again two native
-    calls.  One Function with or without a teacher -- the entry points take the
-    teacher's arguments as NULL for a free-running chain; ``teacher``, ``mask``
-    and ``maps`` are None then.  Flags, seeds, saved, the anchored parameters,
-    both gradient modes and what is returned to autograd are _RolloutTeacher's,
-    with ``ceil(horizon / stride)`` windows."""
-
-    @staticmethod
-    def forward(ctx, model, paired, horizon, stride, obs, teacher, mask, maps, *params):
-        L = native.lib()
-        n, tin, v, c = obs.shape
-        dev = obs.device
-        t = tin + model.output_time_frame
-        windows = -(-horizon // stride)
-        flags = _bn_flags(model) | (native.TRAIN_PAIRED if paired else 0)
-        if getattr(model, "_dstd_one_stream", False):
-            flags |= native.TRAIN_ONE_STREAM
-        drop = float(model.do_in.p) if model.do_in.training else 0.0
-        seeds, ctx.seed_t = None, None
-        if drop > 0:
-            ctx.seed_t = torch.randint(0, 2 ** 62, (windows,), device=dev, dtype=torch.int64)
-            seeds = ctx.seed_t.data_ptr()
-            flags |= native.TRAIN_SEED_DEVICE
-        params_all, buffers = model._tree.get(model)
-        out = obs.new_empty(n, horizon, v, c)
-        nbytes = L.dstd_model_rollout_saved_bytes(n, t, v, model.num_feature, model.num_layers, windows)
-        saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ctx.mask = mask  # the backward reads it again
-        if mask is None:
-            ctx.tf = (None, 0, None, None, None)
-        else:
-            ctx.tf = (native.ptr(teacher, "teacher"), teacher.shape[1], *native.ext_stride_train.frame_maps(maps),
-                      mask.data_ptr())
-        code = L.dstd_model_rollout_strided_fwd(native.ext_stride_train.model_params_ref(model._native_params()),
-                                                native.ptr(obs, "observed"), n, tin, horizon, stride,
-                                                _bn_momentum(model), drop, seeds, native.ptr(out, "out"),
-                                                saved.data_ptr(), nbytes, *ctx.tf, native.stream_handle(dev), flags)
-        native.check(code, "dstd_model_rollout_strided_fwd")
-        if not flags & native.TRAIN_RUNNING_STATS:
-            torch.autograd.graph.increment_version(buffers)
-            _count_batch(model, windows * (2 if paired else 1))
-        ctx.model, ctx.saved_buf, ctx.drop, ctx.flags, ctx.shape = model, saved, drop, flags, (n, tin, v, c)
-        ctx.horizon, ctx.stride = horizon, stride
-        ctx.anchored = len(params) == 1 and params[0] is getattr(model, "_dstd_anchor_t", None)
-        ctx.params = params_all if ctx.anchored else list(params)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        L = native.lib()
-        model = ctx.model
+        model, chain, windows = ctx.model, ctx.chain, ctx.windows
         n, tin, v, c = ctx.shape
         dev = dout.device
         dout = dout.contiguous()
@@ -886,31 +663,39 @@ class _RolloutStrided(torch.autograd.Function):
         arena, direct = None, False
         if ctx.anchored or (getattr(model, "_dstd_inplace_grads", False) and not _param_hooks(ctx.params)):
             arena, direct = native.grad_sink(model, ctx.params, dev)
-        t = tin + model.output_time_frame
-        windows = -(-ctx.horizon // ctx.stride)
-        ws = native.workspace(dev, L.dstd_model_rollout_strided_workspace_bytes(n, t, v, model.num_feature,
-                                                                                model.num_layers, tin, ctx.horizon))
+        size = (n, tin + model.output_time_frame, v, model.num_feature, model.num_layers)
+        if chain.strided:
+            ws = native.workspace(dev, L.dstd_model_rollout_strided_workspace_bytes(*size, tin, ctx.horizon))
+        else:
+            ws = native.workspace(dev, L.dstd_model_rollout_workspace_bytes(*size))
         dobs = dout.new_empty(n, tin, v, c) if need_dx else None
-        pref = native.ext_stride_train.model_params_ref(model._native_params())
+        pref = native.ext.model_params_ref(model._native_params())
         tail = (ctx.drop, ctx.seed_t.data_ptr() if ctx.seed_t is not None else None, ctx.saved_buf.data_ptr(),
                 ctx.saved_buf.numel(), native.ptr(dout, "dout"))
         tail2 = (dobs.data_ptr() if need_dx else None, ws.data_ptr(), ws.numel(), *ctx.tf, native.stream_handle(dev),
                  ctx.flags)
-        gref = native.ext_stride_train.model_grads_ref
-        if direct:  # one (+=) chain into the parameters' .grad
+        if direct:
+            # every window accumulates (+=) into the parameters' .grad, as the K
+            # backwards of a loop do in this mode: one native call
             g = getattr(arena, "model_grads", None)
             if g is None:
                 g = arena.model_grads = model._native_grads(arena)
-            code = L.dstd_model_rollout_strided_bwd(pref, n, tin, ctx.horizon, ctx.stride, *tail, gref(g), *tail2)
-            native.check(code, "dstd_model_rollout_strided_bwd")
-        else:  # an arena per window, summed in backward order (_RolloutTrain.backward says why)
+            code = getattr(L, chain.stem + "_bwd")(pref, n, tin, *ctx.span, *tail, native.ext.model_grads_ref(g),
+                                                   *tail2)
+            native.check(code, chain.stem + "_bwd")
+        else:
+            # gradients for autograd: a zeroed arena per window, summed in backward
+            # order (window K-1 first) -- what autograd makes of the K backwards of
+            # a loop, each of which returns an arena of its own.  One (+=) chain
+            # into a single arena would round alpha_sm, which both spatial
+            # operators of a block add into, differently from that.
             numel = native.arena_numel(ctx.params)
             bufs = torch.zeros(windows, numel, dtype=torch.float32, device=dev)
+            bwd_window = getattr(L, chain.stem + "_bwd_window")
             for k in range(windows - 1, -1, -1):
                 g = model._native_grads(native.GradArena(ctx.params, dev, buf=bufs[k]))
-                code = L.dstd_model_rollout_strided_bwd_window(pref, n, tin, ctx.horizon, ctx.stride, k, *tail, gref(g),
-                                                               *tail2)
-                native.check(code, "dstd_model_rollout_strided_bwd_window")
+                code = bwd_window(pref, n, tin, *ctx.span, k, *tail, native.ext.model_grads_ref(g), *tail2)
+                native.check(code, chain.stem + "_bwd_window")
             total = bufs[windows - 1]
             for k in range(windows - 2, -1, -1):
                 total += bufs[k]
@@ -921,6 +706,7 @@ class _RolloutStrided(torch.autograd.Function):
         if direct:
             return (*head, *([None] * (1 if ctx.anchored else len(arena.params))))
         if ctx.anchored:
+            # .grad was set by someone else since the forward (_ModelTrain.backward)
             for p, gv in zip(arena.params, arena.views()):
                 if gv is not None and p.requires_grad:
                     if p.grad is None:
@@ -931,12 +717,14 @@ class _RolloutStrided(torch.autograd.Function):
         return (*head, *arena.views())
 
 
-class _RolloutStridedPair(torch.autograd.Function):
-    """_RolloutTrainPair over _RolloutStrided."""
+class _RolloutChainPair(torch.autograd.Function):
+    """DSTDGCN.rollout_pair's Function: _RolloutChain over the concatenated
+    pair (DSTD_TRAIN_PAIRED) with the two halves as two outputs, as
+    _ModelTrainPair."""
 
     @staticmethod
     def forward(ctx, model, n, horizon, stride, obs, teacher, mask, maps, *params):
-        out = _RolloutStrided.forward(ctx, model, True, horizon, stride, obs, teacher, mask, maps, *params)
+        out = _RolloutChain.forward(ctx, model, True, horizon, stride, obs, teacher, mask, maps, *params)
         ctx.half = n
         return out[:n], out[n:]
 
@@ -949,7 +737,8 @@ class _RolloutStridedPair(torch.autograd.Function):
             d1 = ref.new_zeros((n, ctx.horizon, v, c))
         if d2 is None:
             d2 = ref.new_zeros((n2 - n, ctx.horizon, v, c))
-        return _RolloutStrided.backward(ctx, torch.cat([d1, d2]))
+        # (argument positions: model, n, ... -- as _RolloutChain's model, paired, ...)
+        return _RolloutChain.backward(ctx, torch.cat([d1, d2]))
 
 
 class BatchNorm(nn.Module):
@@ -1710,14 +1499,8 @@ class DSTDGCN(_NativeModule):
         observed = observed.contiguous()
         if n == 0:  # empty batch: empty output
             return _mark(observed.new_empty(0, horizon, v, c), observed, *params)
-        if stride is not None:
-            return _RolloutStrided.apply(self, False, horizon, stride, observed, teacher if tf else None,
-                                         mask if tf else None, [(0, 1)] if tf else None,
-                                         *_anchor_of(self, observed, params))
-        if tf:
-            return _RolloutTeacher.apply(self, False, horizon, observed, teacher, mask, [(0, 1)],
-                                         *_anchor_of(self, observed, params))
-        return _RolloutTrain.apply(self, False, horizon, observed, *_anchor_of(self, observed, params))
+        return _RolloutChain.apply(self, False, horizon, stride, observed, teacher if tf else None,
+                                   mask if tf else None, [(0, 1)] if tf else None, *_anchor_of(self, observed, params))
 
     def rollout_pair(self, obs1, obs2, horizon=None, teacher=None, teacher_mask=None, stride=None):
         """``(self.rollout(obs1, horizon), self.rollout(obs2, horizon))`` as one
@@ -1751,14 +1534,9 @@ class DSTDGCN(_NativeModule):
             raise RuntimeError("DSTDGCN.rollout_pair: eager only (tensor subclasses cannot be traced through the chain)")
         obs = torch.cat([obs1, obs2]).contiguous()
         params = self._tree.get(self)[0]
-        if stride is not None:
-            maps = [(0, 1), (teacher.shape[1] - 1, -1)] if tf else None
-            return _RolloutStridedPair.apply(self, n, horizon, stride, obs, teacher if tf else None,
-                                             mask if tf else None, maps, *_anchor_of(self, obs, params))
-        if tf:
-            return _RolloutTeacherPair.apply(self, n, horizon, obs, teacher, mask, [(0, 1), (teacher.shape[1] - 1, -1)],
-                                             *_anchor_of(self, obs, params))
-        return _RolloutTrainPair.apply(self, n, horizon, obs, *_anchor_of(self, obs, params))
+        maps = [(0, 1), (teacher.shape[1] - 1, -1)] if tf else None
+        return _RolloutChainPair.apply(self, n, horizon, stride, obs, teacher if tf else None, mask if tf else None,
+                                       maps, *_anchor_of(self, obs, params))
 
     def forward_pair(self, x1, x2):
         """``(self(x1), self(x2))`` -- PredictionEngine.train's forward of a

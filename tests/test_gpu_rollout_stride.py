@@ -215,17 +215,53 @@ def test_a_forced_sample_does_not_see_its_observations_again():
     assert float(o1.grad[1].abs().max()) == 0 and float(o1.grad[0].abs().max()) > 0
 
 
-def test_a_stride_of_a_whole_window_is_the_existing_function_and_eval_is_predict():
+def _record_chain_calls(monkeypatch):
+    """The nine chain entry points of native.lib() behind pass-throughs that
+    note (name, arguments) of every call, for the duration of the test."""
+    L, calls = native.lib(), []
+    for family in ("", "_tf", "_strided"):
+        for step in ("fwd", "bwd", "bwd_window"):
+            name = f"dstd_model_rollout{family}_{step}"
+
+            def through(*args, _fn=getattr(L, name), _name=name):
+                calls.append((_name, args))
+                return _fn(*args)
+            monkeypatch.setattr(L, name, through)
+    return calls
+
+
+def test_a_stride_of_a_whole_window_is_the_existing_function_and_eval_is_predict(monkeypatch):
+    """Which entry points a call reaches, and in which order: stride None and
+    ``output_time_frame`` the plain ones, with a teacher the _tf_ ones, a stride
+    below a window the _strided_ ones with a teacher and without; one forward,
+    then one _bwd in the in-place gradient mode, or K _bwd_window with
+    k = K - 1 .. 0 for autograd; for rollout and rollout_pair alike."""
     m, Tin, V, S, H = case_model(CASES[1])
     a, b = twins(m, "train")
     obs = observations(2, Tin, V, 97)
-    for stride in (None, a.output_time_frame):
-        out = a.rollout(obs.clone().requires_grad_(), H, stride=stride)
-        assert type(out.grad_fn).__name__ == "_RolloutTrainBackward"
-    out = a.rollout(obs.clone().requires_grad_(), H, stride=S)
-    assert type(out.grad_fn).__name__ == "_RolloutStridedBackward"
-    o1, o2 = a.rollout_pair(obs, obs, H, stride=S)
-    assert type(o1.grad_fn).__name__ == "_RolloutStridedPairBackward"
+    truth = observations(2, Tin + H, V, 98)
+    calls = _record_chain_calls(monkeypatch)
+    for pair in (False, True):
+        for stride, teacher, family in ((None, False, ""), (a.output_time_frame, False, ""), (None, True, "_tf"),
+                                        (S, False, "_strided"), (S, True, "_strided")):
+            K = windows(H, stride or a.output_time_frame)
+            tf = dict(teacher=truth, teacher_mask=mask_of("mixed", K, 4 if pair else 2, pair)) if teacher else {}
+            for inplace in (False, True):
+                a._dstd_inplace_grads = inplace
+                a.zero_grad(set_to_none=True)  # (gradients of the other mode would keep the in-place one out)
+                del calls[:]
+                leaves = [obs.clone().requires_grad_() for _ in range(2 if pair else 1)]
+                outs = a.rollout_pair(*leaves, H, stride=stride, **tf) if pair else (
+                    a.rollout(leaves[0], H, stride=stride, **tf),)
+                _loss(outs).backward()
+                stem = f"dstd_model_rollout{family}_"
+                want = [stem + "fwd"] + ([stem + "bwd"] if inplace else [stem + "bwd_window"] * K)
+                what = f"pair={pair} stride={stride} teacher={teacher} inplace={inplace}"
+                assert [name for name, _ in calls] == want, what
+                if not inplace:  # (params, B, input_n, horizon[, stride], k, ...)
+                    at = 5 if family == "_strided" else 4
+                    assert [args[at] for _, args in calls[1:]] == list(range(K - 1, -1, -1)), what
+    a._dstd_inplace_grads = False
     b.eval()
     with torch.no_grad():
         _equal(b.rollout(obs, H, stride=S), b.predict(obs, H, stride=S), "eval, nothing to differentiate")
